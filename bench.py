@@ -21,7 +21,15 @@ components (no data-path collective); the FPSet hash-partitioned by owner
 with the per-level exchange (BASELINE config 4) is measured beside it, and a
 producer-modelled cfg splits the component tree by subtrees.
 
+A plain run sets up, warms up, times the K steps of the headline engine and
+prints the result line.  `--full` adds every other measurement to the line:
+the HBM-FPSet engine and the wave kernels (`engines`), the exchange leg of a
+multi-rank run, and the CPU baseline.  `--dump-outputs DIR` writes what the
+headline engine's last timed step returned (counts, per-level sizes, a seeded
+sample of the stored states) as DIR/<name>.npy.
+
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config g9|m8|s|g9deep|p8]
+                    [--full] [--dump-outputs DIR]
 """
 import argparse
 import json
@@ -282,13 +290,88 @@ def cpu_baseline(cfg, seconds_target=12.0):
                 single_thread=single, wall_s=round(wall + wall_p, 2))
 
 
+# --dump-outputs: the seeded sample of the component engine's store.  Its code
+# pass holds component ci in lane ci % 64 of batch ci // 64, K = 64 queue
+# positions per lane: slot = batch x K x 64 + position x 64 + lane
+# (component.h comp_record); components of K - 1 or more states live elsewhere
+DUMP_SEED, DUMP_COMPONENTS, COMP_CODE_K = 20240601, 512, 64
+
+
+def u64_columns(a):
+    """uint64 array [n, w] -> float64 [n, 2w]: each word as (low 32 bits, high 32 bits), exact"""
+    import numpy as np
+    return np.stack([(a & np.uint64(0xFFFFFFFF)).astype(np.float64), (a >> np.uint64(32)).astype(np.float64)],
+                    axis=-1).reshape(a.shape[0], -1)
+
+
+def component_size(model, ci):
+    """states of component ci (no Producer: the closure of initial state ci), by the host model"""
+    import tlcgpu
+    seen, todo = set(), [tlcgpu.host_init_state(model, ci)]
+    while todo:
+        s = todo.pop()
+        if s not in seen:
+            seen.add(s)
+            todo.extend(t for _, t in tlcgpu.host_successors(model, s))
+    return len(seen)
+
+
+def collect_outputs(ck, counts, levels, sample):
+    """What a caller of the timed path holds after a check, as float64 arrays:
+    `counts` (generated, distinct, depth, status), `levels` (distinct states per
+    BFS level), `level_generated` where the engine keeps it, and -- `sample`:
+    the component engine on one rank, whose store is laid out by component --
+    `states_sample`: the stored states of DUMP_COMPONENTS seeded components,
+    each component's in its queue order (tlcg_copy_states_words), with the
+    component of every row in `states_sample_component`."""
+    import ctypes as C
+    import random
+    import numpy as np
+    import tlcgpu
+    out = {"counts": np.array(counts, dtype=np.float64), "levels": np.array(levels, dtype=np.float64)}
+    try:
+        out["level_generated"] = np.array(ck.level_generated(), dtype=np.float64)
+    except RuntimeError:
+        pass
+    if sample and int(ck.stats.engine) == 2:
+        n_comp, K, w = tlcgpu.init_count(ck.model), COMP_CODE_K, ck.words
+        rng = random.Random(DUMP_SEED)
+        comps = sorted(set(rng.randrange(n_comp) for _ in range(DUMP_COMPONENTS)))
+        buf = (C.c_uint64 * (K * 64 * w))()
+        rows, owner = [np.zeros((0, w), dtype=np.uint64)], []
+        for ci in comps:
+            n = component_size(ck.model, ci)
+            if n >= K - 1:
+                continue
+            base, span = ci // 64 * K * 64 + ci % 64, 64 * (n - 1) + 1
+            ck._chk(ck.lib.tlcg_copy_states_words(ck.ctx, base, span, buf), "tlcg_copy_states_words")
+            rows.append(np.frombuffer(buf, dtype=np.uint64)[:span * w].reshape(span, w)[::64].copy())
+            owner += [ci] * n
+        out["states_sample"] = u64_columns(np.concatenate(rows))
+        out["states_sample_component"] = np.array(owner, dtype=np.float64)
+    return out
+
+
+def write_outputs(path, outputs, rank):
+    """DIR/<name>.npy (rank 0, or the only rank) and DIR/<name>.rank<r>.npy (the other ranks' shares)"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(path, name + (f".rank{rank}" if rank else "") + ".npy"), a)
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default="g9", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the other engines (global HBM FPSet, wave quotient), the multi-rank "
+                         "exchange leg and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the headline engine's last timed step as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (RCCL, one GPU per rank) or gloo (rehearsal)")
     return ap.parse_args(argv)
 
@@ -410,8 +493,9 @@ def main():
     words = tlcgpu.state_words(model)
     import dist as tdist
 
-    def time_engine(engine):
-        """warmup + K timed complete checks with one engine; max over ranks"""
+    def time_engine(engine, dump=False):
+        """warmup + K timed complete checks with one engine; max over ranks
+        (dump: keep the last step's outputs for --dump-outputs)"""
         per_rank = cfg["distinct"] // world + 1
         log2 = max(16, (2 * per_rank - 1).bit_length()) if engine == "global" else 0
         cap = int(per_rank * 1.08) + 2 * (cfg["distinct"] // 12) // world + (1 << 20)
@@ -443,6 +527,8 @@ def main():
         jit = int(st.jit_used)
         launches = len(eng.level_sizes()) if used == "global" else \
             cfg.get("N", 3) + 1 if used == "tree" and cfg.get("producer") else 1
+        outputs = collect_outputs(eng.ck, [st.generated, st.distinct, st.depth, st.status], eng.level_sizes(),
+                                  sample=world == 1 and not open_model) if dump else None
         if distributed:
             t = torch.tensor([elapsed, ems, kms], dtype=torch.float64, device=rdev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -461,7 +547,7 @@ def main():
         if tuple(counts) != (cfg["generated"], cfg["distinct"]):
             raise SystemExit(f"count mismatch ({engine}): {counts} want {cfg}")
         return dict(engine=used, jit=jit, elapsed=elapsed, expand_ms=ems / args.steps, kernel_ms=kms / args.steps,
-                    launches=launches, expansions=expansions)
+                    launches=launches, expansions=expansions, outputs=outputs)
 
     def time_exchange(partition):
         """The global engine with successors crossing ranks, so every BFS level
@@ -497,13 +583,19 @@ def main():
         eng.close()
         if (r.generated, r.distinct, r.depth) != (cfg["generated"], cfg["distinct"], cfg["depth"]):
             raise SystemExit(f"count mismatch (exchange): {(r.generated, r.distinct, r.depth)} want {cfg}")
+        outputs = None
+        if args.dump_outputs:  # the combined result tlcg_run_comm returned (the same on every rank)
+            import numpy as np
+            code = {v: k for k, v in tlcgpu.STATUS.items()}[r.status]
+            outputs = dict(counts=np.array([r.generated, r.distinct, r.depth, code], dtype=np.float64),
+                           levels=np.array(r.levels, dtype=np.float64))
         if r.engine == "tree":  # Producer modelled: each rank ran whole subtrees of the component tree
             return dict(engine="tree", jit=1, elapsed=float(t[0]), expand_ms=float(t[1]) / args.steps,
-                        kernel_ms=float(t[2]) / args.steps, launches=cfg.get("N", 3) + 1,
+                        kernel_ms=float(t[2]) / args.steps, launches=cfg.get("N", 3) + 1, outputs=outputs,
                         partition="component tree, whole subtrees per rank (csrc/tree.h): no exchange",
                         exchange="none on the data path: tlcg_run_comm all-reduces the combined counts over RCCL")
         return dict(engine="global", jit=0, elapsed=float(t[0]), expand_ms=float(t[1]) / args.steps,
-                    kernel_ms=float(t[2]) / args.steps, launches=cfg["depth"] - 1,
+                    kernel_ms=float(t[2]) / args.steps, launches=cfg["depth"] - 1, outputs=outputs,
                     kernel="k_expand<u64, open partition> + k_absorb",
                     partition="whole state (owner = mix64(state))" if partition == 2 else "open (Producer)",
                     exchange="libtlcgpu tlcg_run_comm: ncclAllGather (counts) + grouped ncclSend/ncclRecv "
@@ -521,22 +613,31 @@ def main():
         # FPSet probes, invariants; tree_body.h for the closed tree) -- with
         # the one-walk-per-wavefront kernels switched off
         with per_state_kernels():
-            main_run = time_engine("auto")
+            main_run = time_engine("auto", dump=bool(args.dump_outputs))
         if main_run["jit"] & (8 | 16):
             raise SystemExit("the per-state headline ran a one-walk-per-wavefront kernel")
-        global_run = time_engine("global")  # the HBM-FPSet engine (the north-star design)
+        if args.full:
+            global_run = time_engine("global")  # the HBM-FPSet engine (the north-star design)
         # the wave kernels (component_wave.h, tree_wave.h): one walk of the code
         # graph per wavefront applied to M x 64 components -- a product
         # quotient, reported apart (engines.wave_quotient), never the headline
-        if not open_model:
+        if args.full and not open_model:
             wave_run = time_engine("auto")
             if not (wave_run["jit"] & (8 | 16)):
                 wave_run = None
+    if args.dump_outputs and main_run.get("outputs"):
+        write_outputs(args.dump_outputs, main_run["outputs"], rank)
     distinct, generated = cfg["distinct"], cfg["generated"]
     # (a producer-modelled cfg has one initial state; its Terminating stutters
     # are not counted out of the probes, so its bytes/state is an upper bound)
     n_init = 1 if open_model else (cfg["keys"] + 1) ** 6
-    selfloops = 0 if open_model else n_init * selfloops_per_m(model)
+    selfloops_cache = []
+
+    def selfloops():
+        # (only the global engine's roofline needs the host walk)
+        if not selfloops_cache:
+            selfloops_cache.append(0 if open_model else n_init * selfloops_per_m(model))
+        return selfloops_cache[0]
 
     def survey_roofline(r, kernel):
         """34.7 algorithmic bytes per distinct state x the distinct
@@ -555,7 +656,7 @@ def main():
                           "entry 8 B, g/d = 1.339 FPSet probes of 8 B; x distinct states of one step")
 
     def roofline_global(r):
-        abytes = algorithmic_bytes(distinct, generated, n_init, selfloops, words)
+        abytes = algorithmic_bytes(distinct, generated, n_init, selfloops(), words)
         rf = survey_roofline(r, r.get("kernel") or ("k_expand_fast" if words == 1 and not open_model else
                                                     "k_expand_prod<8> (Producer)" if words == 1 else
                                                     "k_expand<u128> (wide FPSet)"))
@@ -574,7 +675,7 @@ def main():
             rf["traffic_source"] = pmc["_file"]
         micro = load_microbench(MICRO_PROFILE)
         if micro and words == 1:
-            probes = (generated - n_init - selfloops) / world
+            probes = (generated - n_init - selfloops()) / world
             inserts = (distinct - n_init) / world
             bound_ms = (probes / micro["load_nt"] + inserts / micro["cas_new"]) * 1e3
             rf["scattered_access_roofline"] = dict(
@@ -688,6 +789,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": main_s["ms_per_step"],
             "higher_is_better": True,
             "scaling": "strong",
@@ -753,7 +855,9 @@ def main():
         return dict(rccl_ranks=n, counts_exact=ok, levels=r.depth, ms=round(ms, 2))
 
     exchange_run = exchange_error = preflight = None
-    if distributed and not open_model and args.dist_backend != "nccl":
+    if distributed and not open_model and not args.full:
+        exchange_error = "skipped: the exchange leg runs with --full"
+    elif distributed and not open_model and args.dist_backend != "nccl":
         exchange_error = f"skipped: the exchange runs over RCCL, not {args.dist_backend} (a rehearsal backend)"
     elif distributed and not open_model and os.environ.get("TLCG_BENCH_EXCHANGE", "1") != "0":
         # a secondary measurement (BASELINE config 4): its failure (every rank
@@ -793,7 +897,7 @@ def main():
             exchange_error = exchange_error or "failed on another rank"
     if rank == 0:
         line = build_line(exchange_run, exchange_error)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args.config)
         print(json.dumps(line), flush=True)
     if distributed:

@@ -1,6 +1,7 @@
 """Docs helper (CPU): rewrite BASELINE.md's measured-results table from the
 newest round's bench lines, profiles/rNN_bench_<cfg>.json (one JSON line
-each, as bench.py prints it).
+each, as `bench.py --full --config <cfg>` prints it: the table needs the
+line's `engines` and `cpu_baseline`).
 
     python scripts/baseline_table.py [rNN]
 """

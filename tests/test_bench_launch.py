@@ -29,6 +29,29 @@ def test_launch_plan():
     assert b.launch_plan(0, {})[0] == "refuse"
 
 
+def test_plain_run_is_the_default():
+    b = load_bench()
+    a = b.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 3, 1)
+    a = b.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+
+
+def test_dumped_words_are_exact(tmp_path):
+    """--dump-outputs stores a 64-bit word as two float64 columns (low, high 32 bits)"""
+    import numpy as np
+    b = load_bench()
+    words = np.array([[0, 1], [(1 << 64) - 1, (1 << 53) + 1], [0x0123456789ABCDEF, 1 << 63]], dtype=np.uint64)
+    cols = b.u64_columns(words)
+    assert cols.dtype == np.float64 and cols.shape == (3, 4)
+    back = cols[:, 0::2].astype(np.uint64) | (cols[:, 1::2].astype(np.uint64) << np.uint64(32))
+    assert (back == words).all()
+    b.write_outputs(str(tmp_path / "d"), {"states_sample": cols}, 0)
+    b.write_outputs(str(tmp_path / "d"), {"states_sample": cols}, 1)
+    assert sorted(os.listdir(tmp_path / "d")) == ["states_sample.npy", "states_sample.rank1.npy"]
+    assert (np.load(tmp_path / "d" / "states_sample.npy") == cols).all()
+
+
 CHILD = r"""
 import json, os, sys
 r, n = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
