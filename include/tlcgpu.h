@@ -334,7 +334,7 @@ typedef struct tlcg_liveness {
   int32_t holds;          /* 1: every behavior (fair behavior) reaches P */
   int32_t kind;           /* TLCG_LIVE_* */
   int32_t fairness;       /* TLCG_FAIR_* checked */
-  int32_t depth;          /* BFS levels of G' */
+  int32_t depth;          /* non-empty BFS levels of G' (0 when G' is empty) */
   uint64_t states_notp;   /* |G'| */
   uint64_t init_notp;     /* initial states in G' */
   uint64_t edges_notp;    /* non-stuttering transitions into states of G' (from states of G') */
@@ -351,6 +351,20 @@ typedef struct tlcg_liveness {
 int tlcg_check_termination(const tlcg_model* m, const tlcg_opts* o, int32_t fairness, tlcg_liveness* out,
                            uint64_t* states, int32_t* actions, int32_t cap, int32_t* len, char* err,
                            int32_t err_cap);
+/* Self-test of the liveness pass on a graph the caller supplies instead of
+ * the spec's (whose G' is acyclic for every cfg): the same kernels, peeling
+ * and lasso extraction over a CSR graph of n nodes -- row[n + 1] offsets into
+ * col[], is_p[n] the nodes that satisfy P, nodes 0 .. n_init - 1 initial.
+ * Move k of node v is edge row[v] + k; a self-loop is a stuttering step, a
+ * repeated edge counts each time.  Node v's state is the word v (words = 1),
+ * or the two words {v, v >> 3} (words = 2, the wide FPSet).  Fills *out and
+ * the counterexample like tlcg_check_termination; actions[i] is the ordinal
+ * k of the edge into states[i] (TLCG_ACT_INIT first), back_action likewise.
+ * Returns 0, -1 on a malformed graph, < -1 on a device error. */
+int tlcg_liveness_graph_selftest(const uint32_t* row, const uint32_t* col, const uint8_t* is_p, uint32_t n,
+                                 uint32_t n_init, int32_t words, const tlcg_opts* o, int32_t fairness,
+                                 tlcg_liveness* out, uint64_t* states, int32_t* actions, int32_t cap, int32_t* len,
+                                 char* err, int32_t err_cap);
 
 /* Enable xGMI peer access among devices 0..n-1 (one process driving contexts
  * on several devices, e.g. tlc-hip -gpus N).  Returns the pairs enabled. */

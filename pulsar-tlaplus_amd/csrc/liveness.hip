@@ -44,6 +44,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <unordered_map>
@@ -51,6 +52,7 @@
 
 #include "host_model.h"
 #include "kernels.h"
+#include "liveness_graph.h"
 #include "tlcgpu.h"
 
 using namespace tlcg;
@@ -73,9 +75,11 @@ struct LvCtr {
   unsigned int pad;
 };
 
-template <typename W>
+// G: the graph policy (liveness_graph.h)
+template <typename G>
 struct LvBufs {
-  Layout L;
+  using W = typename G::word;
+  G g;
   u64* slots;     // FPSet, 2^log2 slots (8 B, or 16 B wide)
   int log2;
   W* store;       // states of G' in BFS order
@@ -123,38 +127,6 @@ __device__ __forceinline__ void block_claim(const bool* pred, u64* at, unsigned 
   __syncthreads();  // (s_wcnt / s_base are reused by the next call)
 }
 
-template <typename W>
-__host__ __device__ inline bool lv_p(const Layout& L, W s) {
-  return terminating_enabled(L, s);
-}
-
-// Move k of s (k < moves_bound(L)): Producer's nkv successors (key outer,
-// value inner), then the compactor disjunct, then BrokerCrash.  Returns 1 with
-// *t / *ord set when that move exists and changes the state, 0 otherwise, 2 on
-// an evaluation error.  Stutters (Consumer, Terminating) are never moves.
-template <typename W>
-__host__ __device__ inline int lv_move(const Layout& L, W s, int k, W* t, int* ord) {
-  const int np = L.producer ? L.nkv : 0;
-  if (k < np) {
-    const int len = st_len(L, s);
-    if (len >= L.N) return 0;
-    *t = producer_succ(L, s, len, k);
-    *ord = ordinal_of(L, ACT_PRODUCER, k);
-    return *t != s;
-  }
-  int act = 0;
-  if (k == np) {
-    const int r = compactor_step(L, s, t, &act);
-    if (r == 2) return 2;
-    *ord = ordinal_of(L, act, 0);
-    return r == 1 && *t != s;
-  }
-  if (!crash_step(L, s, t)) return 0;
-  *ord = ordinal_of(L, ACT_CRASH, 0);
-  return *t != s;
-}
-__host__ __device__ inline int moves_bound(const Layout& L) { return (L.producer ? L.nkv : 0) + 2; }
-
 // FPSet lookup of a state known to be present (all inserts finished in an
 // earlier launch, so plain loads see every slot).
 template <typename W>
@@ -178,8 +150,9 @@ __device__ __forceinline__ u64 lv_lookup(const u64* slots, int log2, W t) {
 
 // insert t (a not-P state) with parent reference pref; every thread of the
 // block calls it (want = this lane has a state to insert)
-template <typename W>
-__device__ __forceinline__ void lv_insert(const LvBufs<W>& B, bool want, W t, u64 pref, bool edge) {
+template <typename G>
+__device__ __forceinline__ void lv_insert(const LvBufs<G>& B, bool want, typename G::word t, u64 pref, bool edge) {
+  using W = typename G::word;
   u64 slot = 0;
   int r = 0;
   if (want) {
@@ -209,9 +182,10 @@ __device__ __forceinline__ void lv_insert(const LvBufs<W>& B, bool want, W t, u6
 // two-word insert one by one.  slot[j] gets the candidate's slot, fresh[j]
 // whether this lane inserted it.
 constexpr int LV_BATCH = 4;
-template <typename W>
-__device__ __forceinline__ void lv_put_batch(const LvBufs<W>& B, const bool* want, const W* t, u64* slot,
-                                             bool* fresh) {
+template <typename G>
+__device__ __forceinline__ void lv_put_batch(const LvBufs<G>& B, const bool* want, const typename G::word* t,
+                                             u64* slot, bool* fresh) {
+  using W = typename G::word;
   if constexpr (sizeof(W) == 8) {
     const int sh = 64 - B.log2;
     const u64 mask = (1ull << B.log2) - 1;
@@ -257,8 +231,10 @@ __device__ __forceinline__ void lv_put_batch(const LvBufs<W>& B, const bool* wan
 }
 
 // the same for lookups of states known to be present: first slots together
-template <typename W>
-__device__ __forceinline__ void lv_lookup_batch(const LvBufs<W>& B, const bool* want, const W* t, u64* slot) {
+template <typename G>
+__device__ __forceinline__ void lv_lookup_batch(const LvBufs<G>& B, const bool* want, const typename G::word* t,
+                                                u64* slot) {
+  using W = typename G::word;
   if constexpr (sizeof(W) == 8) {
     const int sh = 64 - B.log2;
     const u64 mask = (1ull << B.log2) - 1;
@@ -290,16 +266,18 @@ __device__ __forceinline__ void lv_lookup_batch(const LvBufs<W>& B, const bool* 
   }
 }
 
-template <typename W>
-__global__ __launch_bounds__(LV_BLOCK) void k_lv_init(LvBufs<W> B, u64 n_init) {
+template <typename G>
+__global__ __launch_bounds__(LV_BLOCK) void k_lv_init(LvBufs<G> B) {
+  using W = typename G::word;
+  const u64 n_init = B.g.n_init();
   const u64 stride = (u64)gridDim.x * LV_BLOCK;
   for (u64 base = (u64)blockIdx.x * LV_BLOCK; base < n_init; base += stride) {
     const u64 i = base + threadIdx.x;
     bool want = false;
     W s = 0;
     if (i < n_init) {
-      s = init_state<W>(B.L, i);
-      want = !lv_p(B.L, s);
+      s = B.g.init(i);
+      want = !B.g.is_p(s);
     }
     // the first not-P initial state: the wave's lowest such index, one atomic per wave
     const u64 wm = __ballot(want);
@@ -309,10 +287,11 @@ __global__ __launch_bounds__(LV_BLOCK) void k_lv_init(LvBufs<W> B, u64 n_init) {
 }
 
 // one BFS level of G': states [a, b)
-template <typename W>
-__global__ __launch_bounds__(LV_BLOCK) void k_lv_expand(LvBufs<W> B, u64 a, u64 b, int fair) {
-  const Layout& L = B.L;
-  const int kmax = moves_bound(L);
+template <typename G>
+__global__ __launch_bounds__(LV_BLOCK) void k_lv_expand(LvBufs<G> B, u64 a, u64 b, int fair) {
+  using W = typename G::word;
+  const G& gr = B.g;
+  const int kmax = gr.moves_bound(), ord_bits = gr.ord_bits();
   const u64 stride = (u64)gridDim.x * LV_BLOCK;
   // edges and stuck states are summed in registers over the whole loop and
   // added once per wave at the end (atomics on one counter serialize)
@@ -333,10 +312,10 @@ __global__ __launch_bounds__(LV_BLOCK) void k_lv_expand(LvBufs<W> B, u64 a, u64 
       for (int j = 0; j < LV_BATCH; ++j) {
         t[j] = 0;
         ord[j] = 0;
-        const int r = live && k0 + j < kmax ? lv_move(L, s, k0 + j, &t[j], &ord[j]) : 0;
+        const int r = live && k0 + j < kmax ? gr.move(s, k0 + j, &t[j], &ord[j]) : 0;
         serr |= r == 2;
         moves += r == 1;
-        want[j] = r == 1 && !lv_p(L, t[j]);
+        want[j] = r == 1 && !gr.is_p(t[j]);
         edges += want[j];
       }
       lv_put_batch(B, want, t, slot, fresh);
@@ -351,7 +330,7 @@ __global__ __launch_bounds__(LV_BLOCK) void k_lv_expand(LvBufs<W> B, u64 a, u64 
             atomicOr(&B.ctr->flags, (unsigned)LV_STORE);
           } else {
             B.store[at] = t[j];
-            B.parent[at] = (g << L.ord_bits) | (u64)ord[j];
+            B.parent[at] = (g << ord_bits) | (u64)ord[j];
             B.slot_of[at] = (u32)slot[j];
             B.gidx_of[slot[j]] = (u32)at;
           }
@@ -372,8 +351,9 @@ __global__ __launch_bounds__(LV_BLOCK) void k_lv_expand(LvBufs<W> B, u64 a, u64 
 }
 
 // the least stuck state of level [a, b): its high word, then its low word, then its index
-template <typename W>
-__global__ __launch_bounds__(LV_BLOCK) void k_lv_pick(LvBufs<W> B, u64 a, u64 b, int phase) {
+template <typename G>
+__global__ __launch_bounds__(LV_BLOCK) void k_lv_pick(LvBufs<G> B, u64 a, u64 b, int phase) {
+  using W = typename G::word;
   const u64 stride = (u64)gridDim.x * LV_BLOCK;
   for (u64 g = a + (u64)blockIdx.x * LV_BLOCK + threadIdx.x; g < b; g += stride) {
     if (!B.stuck[g]) continue;
@@ -386,8 +366,8 @@ __global__ __launch_bounds__(LV_BLOCK) void k_lv_pick(LvBufs<W> B, u64 a, u64 b,
 }
 
 // Kahn peeling: the states of in-degree 0 ...
-template <typename W>
-__global__ __launch_bounds__(LV_BLOCK) void k_lv_zero(LvBufs<W> B, u64 n, u32* list) {
+template <typename G>
+__global__ __launch_bounds__(LV_BLOCK) void k_lv_zero(LvBufs<G> B, u64 n, u32* list) {
   const u64 stride = (u64)gridDim.x * LV_BLOCK;
   for (u64 base = (u64)blockIdx.x * LV_BLOCK; base < n; base += stride) {
     const u64 g = base + threadIdx.x;
@@ -400,10 +380,11 @@ __global__ __launch_bounds__(LV_BLOCK) void k_lv_zero(LvBufs<W> B, u64 n, u32* l
 
 // ... then, per round, remove them: each successor in G' loses one in-edge,
 // and the ones that reach 0 form the next round
-template <typename W>
-__global__ __launch_bounds__(LV_BLOCK) void k_lv_peel(LvBufs<W> B, const u32* list, u64 n, u32* next) {
-  const Layout& L = B.L;
-  const int kmax = moves_bound(L);
+template <typename G>
+__global__ __launch_bounds__(LV_BLOCK) void k_lv_peel(LvBufs<G> B, const u32* list, u64 n, u32* next) {
+  using W = typename G::word;
+  const G& gr = B.g;
+  const int kmax = gr.moves_bound();
   const u64 stride = (u64)gridDim.x * LV_BLOCK;
   for (u64 base = (u64)blockIdx.x * LV_BLOCK; base < n; base += stride) {
     const u64 i = base + threadIdx.x;
@@ -417,7 +398,7 @@ __global__ __launch_bounds__(LV_BLOCK) void k_lv_peel(LvBufs<W> B, const u32* li
       for (int j = 0; j < LV_BATCH; ++j) {
         t[j] = 0;
         int ord = 0;
-        want[j] = live && k0 + j < kmax && lv_move(L, s, k0 + j, &t[j], &ord) == 1 && !lv_p(L, t[j]);
+        want[j] = live && k0 + j < kmax && gr.move(s, k0 + j, &t[j], &ord) == 1 && !gr.is_p(t[j]);
       }
       lv_lookup_batch(B, want, t, slot);
       bool freed[LV_BATCH];
@@ -445,8 +426,8 @@ __global__ __launch_bounds__(LV_BLOCK) void k_lv_peel(LvBufs<W> B, const u32* li
 }
 
 // the states left after peeling (on or after a cycle): their indices
-template <typename W>
-__global__ __launch_bounds__(LV_BLOCK) void k_lv_left(LvBufs<W> B, u64 n, u32* list) {
+template <typename G>
+__global__ __launch_bounds__(LV_BLOCK) void k_lv_left(LvBufs<G> B, u64 n, u32* list) {
   const u64 stride = (u64)gridDim.x * LV_BLOCK;
   for (u64 base = (u64)blockIdx.x * LV_BLOCK; base < n; base += stride) {
     const u64 g = base + threadIdx.x;
@@ -457,9 +438,16 @@ __global__ __launch_bounds__(LV_BLOCK) void k_lv_left(LvBufs<W> B, u64 n, u32* l
   }
 }
 
-unsigned grid_for(u64 n) {
+// TLCG_LV_GRID=n caps the grid of every kernel of the pass (a test hook: one
+// block then takes every grid-stride chunk); 0 or unset: no cap
+unsigned lv_grid_cap() {
+  const char* v = std::getenv("TLCG_LV_GRID");
+  const long c = v ? std::atol(v) : 0;
+  return c > 0 ? (unsigned)std::min<long>(c, 256 * 32) : 256 * 32;
+}
+unsigned lv_grid(u64 n, unsigned cap) {
   const u64 blocks = (n + LV_BLOCK - 1) / LV_BLOCK;
-  return (unsigned)std::max<u64>(1, std::min<u64>(blocks, 256 * 32));
+  return (unsigned)std::max<u64>(1, std::min<u64>(blocks, cap));
 }
 
 struct DevMem {
@@ -492,8 +480,10 @@ struct LvTrace {
 };
 
 // BFS path from Init to stored state g (states and the actions into them)
-template <typename W>
-int path_to(const LvBufs<W>& B, u64 g, LvTrace* tr, std::string* err) {
+template <typename G>
+int path_to(const LvBufs<G>& B, const G& hg, u64 g, LvTrace* tr, std::string* err) {
+  using W = typename G::word;
+  const int ord_bits = hg.ord_bits();
   std::vector<std::pair<W, u64>> rev;
   for (;;) {
     W s;
@@ -502,92 +492,25 @@ int path_to(const LvBufs<W>& B, u64 g, LvTrace* tr, std::string* err) {
     LV_CHECK(hipMemcpy(&p, B.parent + g, sizeof(u64), hipMemcpyDeviceToHost));
     rev.push_back({s, p});
     if (p == NO_PARENT || rev.size() > 1u << 20) break;
-    g = p >> B.L.ord_bits;
+    g = p >> ord_bits;
   }
   for (size_t i = rev.size(); i-- > 0;) {
     tr->states.push_back((u128)rev[i].first);
     const u64 p = rev[i].second;
     tr->actions.push_back(p == NO_PARENT ? TLCG_ACT_INIT
-                                         : action_of_ordinal(B.L, (int)(p & ((1ull << B.L.ord_bits) - 1))));
+                                         : hg.action_of((int)(p & ((1ull << ord_bits) - 1))));
   }
   return 0;
 }
 
-// Host: the states left after peeling (st, with their BFS indices idx,
-// ascending) lie on cycles or after them.  Peel them from the other side
-// (drop states none of whose successors is left) so that every remaining state
-// has a successor among them, then walk from the shallowest remaining state,
-// taking the first remaining successor in Next order, until a state repeats.
-// The lasso: *g_entry (the repeated state's BFS index), the cycle's other
-// states with the actions into them, and the action back to the entry.
-template <typename W>
-int lasso_walk(const Layout& L, const std::vector<W>& st, const std::vector<u32>& idx, u64* g_entry,
-               std::vector<u128>* cyc, std::vector<int>* cyc_act, int* back_action, std::string* err) {
-  const size_t n = st.size();
-  std::vector<std::pair<W, u32>> by_state(n);
-  for (size_t i = 0; i < n; ++i) by_state[i] = {st[i], (u32)i};
-  std::sort(by_state.begin(), by_state.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
-  auto find = [&](W t) -> long {
-    auto it = std::lower_bound(by_state.begin(), by_state.end(), t,
-                               [](const std::pair<W, u32>& a, W v) { return a.first < v; });
-    return it != by_state.end() && it->first == t ? (long)it->second : -1;
-  };
-  const int kmax = moves_bound(L);
-  std::vector<std::vector<std::pair<u32, int>>> succ(n);  // (state, ordinal) in Next order
-  std::vector<std::vector<u32>> pred(n);
-  for (size_t i = 0; i < n; ++i)
-    for (int k = 0; k < kmax; ++k) {
-      W t;
-      int ord = 0;
-      if (lv_move(L, st[i], k, &t, &ord) != 1 || lv_p(L, t)) continue;
-      const long j = find(t);
-      if (j < 0) continue;
-      succ[i].push_back({(u32)j, ord});
-      pred[j].push_back((u32)i);
-    }
-  std::vector<size_t> outc(n);
-  std::vector<char> alive(n, 1);
-  std::vector<u32> q;
-  for (size_t i = 0; i < n; ++i)
-    if ((outc[i] = succ[i].size()) == 0) q.push_back((u32)i);
-  while (!q.empty()) {
-    const u32 v = q.back();
-    q.pop_back();
-    alive[v] = 0;
-    for (u32 p : pred[v])
-      if (alive[p] && --outc[p] == 0) q.push_back(p);
-  }
-  size_t start = 0;
-  while (start < n && !alive[start]) ++start;
-  if (start == n) {
-    *err = "liveness: peeling left states but no cycle among them";
-    return -1;
-  }
-  std::vector<long> seen(n, -1);
-  std::vector<u32> walk;
-  std::vector<int> ords;
-  u32 v = (u32)start;
-  while (seen[v] < 0) {
-    seen[v] = (long)walk.size();
-    walk.push_back(v);
-    const auto* nx = &succ[v][0];
-    while (!alive[nx->first]) ++nx;  // one exists: v kept a live successor
-    ords.push_back(nx->second);
-    v = nx->first;
-  }
-  const size_t c0 = (size_t)seen[v];
-  *g_entry = idx[walk[c0]];
-  for (size_t i = c0 + 1; i < walk.size(); ++i) {
-    cyc->push_back((u128)st[walk[i]]);
-    cyc_act->push_back(action_of_ordinal(L, ords[i - 1]));
-  }
-  *back_action = action_of_ordinal(L, ords.back());
-  return 0;
-}
-
-template <typename W>
-int run_liveness(const HostModel& hm, const tlcg_opts* o, int fair, tlcg_liveness* out, LvTrace* tr, std::string* err) {
-  const Layout& L = hm.L;
+// dg: the graph as the kernels read it, hg: as the host reads it (the same
+// object for ModelGraph; device and host copies of the arrays for ExplicitGraph)
+template <typename G>
+int run_liveness(const G& dg, const G& hg, const tlcg_opts* o, int fair, tlcg_liveness* out, LvTrace* tr,
+                 std::string* err) {
+  using W = typename G::word;
+  const unsigned grid_cap = lv_grid_cap();
+  auto grid_for = [grid_cap](u64 n) { return lv_grid(n, grid_cap); };
   u64 cap = o && o->state_capacity ? o->state_capacity : (u64)1 << 22;
   int log2 = o && o->log2_fpset_slots > 0 ? o->log2_fpset_slots : 0;
   hipEvent_t e0, e1;
@@ -612,8 +535,8 @@ int run_liveness(const HostModel& hm, const tlcg_opts* o, int fair, tlcg_livenes
     }
     if (lg > 32) lg = 32;
     DevMem mem;
-    LvBufs<W> B;
-    B.L = L;
+    LvBufs<G> B;
+    B.g = dg;
     B.log2 = lg;
     B.cap = cap;
     const u64 nslots = 1ull << lg;
@@ -645,7 +568,7 @@ int run_liveness(const HostModel& hm, const tlcg_opts* o, int fair, tlcg_livenes
     };
     float ms_total = 0.f, ms = 0.f;
     LV_CHECK(hipEventRecord(e0, 0));
-    k_lv_init<W><<<grid_for(hm.n_init), LV_BLOCK>>>(B, hm.n_init);
+    k_lv_init<G><<<grid_for(hg.n_init()), LV_BLOCK>>>(B);
     LV_CHECK(hipGetLastError());
     if (read_ctr()) return -4;
     std::vector<u64> level_base{0, std::min<u64>(h.n, cap)}, level_stuck;
@@ -653,7 +576,7 @@ int run_liveness(const HostModel& hm, const tlcg_opts* o, int fair, tlcg_livenes
     while (!again && level_base.back() > level_base[level_base.size() - 2]) {
       const u64 a = level_base[level_base.size() - 2], b = level_base.back();
       LV_CHECK(hipMemset(&B.ctr->stuck, 0, sizeof(unsigned long long)));
-      k_lv_expand<W><<<grid_for(b - a), LV_BLOCK>>>(B, a, b, fair);
+      k_lv_expand<G><<<grid_for(b - a), LV_BLOCK>>>(B, a, b, fair);
       LV_CHECK(hipGetLastError());
       if (read_ctr()) return -4;
       if (h.flags & LV_EVAL) {
@@ -676,7 +599,7 @@ int run_liveness(const HostModel& hm, const tlcg_opts* o, int fair, tlcg_livenes
     out->states_notp = n;
     out->init_notp = level_base[1];
     out->edges_notp = h.edges;
-    out->depth = (int32_t)(level_base.size() - 2 + (n > 0 ? 1 : 0));
+    out->depth = (int32_t)(level_base.size() - 2);  // (the last entry repeats: the empty level that ended the BFS)
     out->stuck = 0;
     for (u64 x : level_stuck) out->stuck += x;
     // 2. Kahn peeling
@@ -687,7 +610,7 @@ int run_liveness(const HostModel& hm, const tlcg_opts* o, int fair, tlcg_livenes
     }
     LV_CHECK(hipEventRecord(e0, 0));
     LV_CHECK(hipMemset(&B.ctr->next, 0, sizeof(unsigned long long)));
-    k_lv_zero<W><<<grid_for(n), LV_BLOCK>>>(B, n, la);
+    k_lv_zero<G><<<grid_for(n), LV_BLOCK>>>(B, n, la);
     LV_CHECK(hipGetLastError());
     if (read_ctr()) return -4;
     u64 removed = 0, cur = h.next;
@@ -696,7 +619,7 @@ int run_liveness(const HostModel& hm, const tlcg_opts* o, int fair, tlcg_livenes
       removed += cur;
       ++rounds;
       LV_CHECK(hipMemset(&B.ctr->next, 0, sizeof(unsigned long long)));
-      k_lv_peel<W><<<grid_for(cur), LV_BLOCK>>>(B, la, cur, lb);
+      k_lv_peel<G><<<grid_for(cur), LV_BLOCK>>>(B, la, cur, lb);
       LV_CHECK(hipGetLastError());
       if (read_ctr()) return -4;
       if (h.flags & LV_LOOKUP) {
@@ -719,7 +642,7 @@ int run_liveness(const HostModel& hm, const tlcg_opts* o, int fair, tlcg_livenes
       // the first not-P initial state in Init order, then stuttering
       out->holds = 0;
       out->kind = TLCG_LIVE_STUTTERING;
-      tr->states.push_back((u128)init_state<W>(L, h.first_init));
+      tr->states.push_back((u128)hg.init(h.first_init));
       tr->actions.push_back(TLCG_ACT_INIT);
       return 0;
     }
@@ -732,14 +655,14 @@ int run_liveness(const HostModel& hm, const tlcg_opts* o, int fair, tlcg_livenes
       h.key_hi = h.key_lo = ~0ull;
       h.pick = ~0ull;
       LV_CHECK(hipMemcpy(B.ctr, &h, sizeof h, hipMemcpyHostToDevice));
-      for (int ph = 0; ph < 3; ++ph) k_lv_pick<W><<<grid_for(b - a), LV_BLOCK>>>(B, a, b, ph);
+      for (int ph = 0; ph < 3; ++ph) k_lv_pick<G><<<grid_for(b - a), LV_BLOCK>>>(B, a, b, ph);
       LV_CHECK(hipGetLastError());
       if (read_ctr()) return -4;
       if (h.pick == ~0ull) {
         *err = "liveness: no stuck state found in its level";
         return -6;
       }
-      return path_to(B, h.pick, tr, err);
+      return path_to(B, hg, h.pick, tr, err);
     }
     if (removed == n) {
       out->holds = 1;
@@ -755,7 +678,7 @@ int run_liveness(const HostModel& hm, const tlcg_opts* o, int fair, tlcg_livenes
       return -5;
     }
     LV_CHECK(hipMemset(&B.ctr->next, 0, sizeof(unsigned long long)));
-    k_lv_left<W><<<grid_for(n), LV_BLOCK>>>(B, n, la);
+    k_lv_left<G><<<grid_for(n), LV_BLOCK>>>(B, n, la);
     LV_CHECK(hipGetLastError());
     std::vector<u32> idx(left);
     std::vector<W> st(left);
@@ -766,15 +689,65 @@ int run_liveness(const HostModel& hm, const tlcg_opts* o, int fair, tlcg_livenes
     std::vector<u128> cyc;
     std::vector<int> cyc_act;
     int back = -1;
-    if (lasso_walk(L, st, idx, &g_entry, &cyc, &cyc_act, &back, err) != 0) return -6;
+    if (lasso_walk(hg, st, idx, &g_entry, &cyc, &cyc_act, &back, err) != 0) return -6;
     // the BFS path to the cycle's entry, then around the cycle back to it
-    if (path_to(B, g_entry, tr, err)) return -4;
+    if (path_to(B, hg, g_entry, tr, err)) return -4;
     tr->loop_to = (int)tr->states.size() - 1;
     tr->states.insert(tr->states.end(), cyc.begin(), cyc.end());
     tr->actions.insert(tr->actions.end(), cyc_act.begin(), cyc_act.end());
     tr->back_action = back;
     return 0;
   }
+}
+
+// the counterexample into the caller's arrays
+void lv_copy_out(const LvTrace& tr, int words, tlcg_liveness* out, uint64_t* states, int32_t* actions, int32_t cap,
+                 int32_t* len) {
+  out->trace_len = (int32_t)tr.states.size();
+  out->loop_to = tr.loop_to;
+  out->back_action = tr.back_action;
+  if (states && actions && len) {
+    const int32_t n = std::min<int32_t>(cap, out->trace_len);
+    for (int32_t i = 0; i < n; ++i) {
+      split_words(tr.states[i], states + (size_t)i * words, words);
+      actions[i] = tr.actions[i];
+    }
+    *len = n;
+  }
+}
+
+template <typename W>
+int run_model(const HostModel& hm, const tlcg_opts* o, int fair, tlcg_liveness* out, LvTrace* tr, std::string* err) {
+  ModelGraph<W> g;
+  g.L = hm.L;
+  g.n_init_ = hm.n_init;
+  return run_liveness(g, g, o, fair, out, tr, err);
+}
+
+// the caller's CSR graph: checked, copied to the device, walked
+template <typename W>
+int run_explicit(const uint32_t* row, const uint32_t* col, const uint8_t* is_p, uint32_t n, uint32_t n_init,
+                 const tlcg_opts* o, int fair, tlcg_liveness* out, LvTrace* tr, std::string* err) {
+  ExplicitGraph<W> hg{};
+  if (!explicit_graph_shape(row, col, n, n_init, &hg, err)) return -1;
+  hg.row = row;
+  hg.col = col;
+  hg.p = is_p;
+  DevMem mem;
+  uint32_t *d_row = nullptr, *d_col = nullptr;
+  unsigned char* d_p = nullptr;
+  if (!mem.alloc(&d_row, (u64)n + 1) || !mem.alloc(&d_col, row[n]) || !mem.alloc(&d_p, n)) {
+    *err = "graph: device allocation failed";
+    return -5;
+  }
+  LV_CHECK(hipMemcpy(d_row, row, ((size_t)n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
+  if (row[n]) LV_CHECK(hipMemcpy(d_col, col, (size_t)row[n] * sizeof(uint32_t), hipMemcpyHostToDevice));
+  if (n) LV_CHECK(hipMemcpy(d_p, is_p, n, hipMemcpyHostToDevice));
+  ExplicitGraph<W> dg = hg;
+  dg.row = d_row;
+  dg.col = d_col;
+  dg.p = d_p;
+  return run_liveness(dg, hg, o, fair, out, tr, err);
 }
 
 }  // namespace
@@ -798,20 +771,41 @@ extern "C" int tlcg_check_termination(const tlcg_model* m, const tlcg_opts* o, i
   const auto t0 = std::chrono::steady_clock::now();
   LvTrace tr;
   const int words = state_words(hm.L);
-  const int rc = words == 1 ? run_liveness<u64>(hm, o, fairness, out, &tr, &e)
-                            : run_liveness<u128>(hm, o, fairness, out, &tr, &e);
+  const int rc = words == 1 ? run_model<u64>(hm, o, fairness, out, &tr, &e)
+                            : run_model<u128>(hm, o, fairness, out, &tr, &e);
   out->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (rc) return fail(rc, e);
-  out->trace_len = (int32_t)tr.states.size();
-  out->loop_to = tr.loop_to;
-  out->back_action = tr.back_action;
-  if (states && actions && len) {
-    const int32_t n = std::min<int32_t>(cap, out->trace_len);
-    for (int32_t i = 0; i < n; ++i) {
-      split_words(tr.states[i], states + (size_t)i * words, words);
-      actions[i] = tr.actions[i];
-    }
-    *len = n;
+  lv_copy_out(tr, words, out, states, actions, cap, len);
+  return 0;
+}
+
+extern "C" int tlcg_liveness_graph_selftest(const uint32_t* row, const uint32_t* col, const uint8_t* is_p, uint32_t n,
+                                            uint32_t n_init, int32_t words, const tlcg_opts* o, int32_t fairness,
+                                            tlcg_liveness* out, uint64_t* states, int32_t* actions, int32_t cap,
+                                            int32_t* len, char* err, int32_t err_cap) {
+  auto fail = [&](int rc, const std::string& e) {
+    if (err && err_cap > 0) std::snprintf(err, (size_t)err_cap, "%s", e.c_str());
+    return rc;
+  };
+  if (!row || !out || (n && !is_p)) return fail(-1, "null argument");
+  if (fairness != TLCG_FAIR_NONE && fairness != TLCG_FAIR_WF_NEXT) return fail(-1, "unknown fairness");
+  if (words != 1 && words != 2) return fail(-1, "words must be 1 or 2");
+  if (row[n] && !col) return fail(-1, "null argument");
+  std::memset(out, 0, sizeof *out);
+  out->fairness = fairness;
+  if (len) *len = 0;
+  std::string e;
+  {  // a malformed graph is refused before the device is touched
+    ExplicitGraph<u64> shape{};
+    if (!explicit_graph_shape(row, col, n, n_init, &shape, &e)) return fail(-1, e);
   }
+  if (hipSetDevice(o ? o->device : 0) != hipSuccess) return fail(-4, "hipSetDevice failed");
+  const auto t0 = std::chrono::steady_clock::now();
+  LvTrace tr;
+  const int rc = words == 1 ? run_explicit<u64>(row, col, is_p, n, n_init, o, fairness, out, &tr, &e)
+                            : run_explicit<u128>(row, col, is_p, n, n_init, o, fairness, out, &tr, &e);
+  out->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (rc) return fail(rc, e);
+  lv_copy_out(tr, words, out, states, actions, cap, len);
   return 0;
 }

@@ -150,6 +150,10 @@ def load_library(path: str = LIB_PATH):
         "tlcg_run_comm": (C.c_int, [P, S, C.POINTER(U64), I32, C.POINTER(I32)]),
         "tlcg_check_termination": (C.c_int, [M, O, I32, C.POINTER(tlcg_liveness), C.POINTER(U64),
                                              C.POINTER(I32), I32, C.POINTER(I32), C.c_char_p, I32]),
+        "tlcg_liveness_graph_selftest": (C.c_int, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                                   C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32, I32, O, I32,
+                                                   C.POINTER(tlcg_liveness), C.POINTER(U64), C.POINTER(I32), I32,
+                                                   C.POINTER(I32), C.c_char_p, I32]),
         "tlcg_jit_selftest": (C.c_int, [M, C.c_char_p, I32, C.c_char_p, I32][:1] + [C.c_char_p, C.c_char_p, I32]),
     }
     for name, (res, args) in sig.items():
@@ -385,6 +389,37 @@ def check_termination(model: Model, fairness: str = "none", device: int = 0, sta
     return Liveness(bool(out.holds), LIVE_KINDS[out.kind], fairness, out.depth, out.states_notp, out.init_notp,
                     out.edges_notp, out.stuck, out.on_cycles, out.peel_rounds, trace, out.loop_to,
                     ACTIONS[out.back_action] if out.loop_to >= 0 else None, out.kernel_ms, out.wall_ms)
+
+
+def liveness_graph(row: Sequence[int], col: Sequence[int], is_p: Sequence[int], n_init: int, words: int = 1,
+                   fairness: str = "none", device: int = 0, state_capacity: int = 0,
+                   log2_fpset_slots: int = 0) -> Liveness:
+    """The liveness pass on an explicit CSR graph (tlcg_liveness_graph_selftest):
+    row[n + 1], col[], is_p[n], nodes 0 .. n_init - 1 initial.  The trace holds
+    (edge ordinal into it or "Init", state word); back_action is an ordinal."""
+    lib = load_library()
+    n = len(is_p)
+    if len(row) != n + 1 or len(col) != row[n]:
+        raise ValueError("row must hold n + 1 offsets, the last one len(col)")
+    c_row = (C.c_uint32 * (n + 1))(*row)
+    c_col = (C.c_uint32 * max(1, len(col)))(*col)
+    c_p = (C.c_uint8 * max(1, n))(*is_p)
+    o = tlcg_opts()
+    o.device, o.state_capacity, o.log2_fpset_slots = device, state_capacity, log2_fpset_slots
+    out = tlcg_liveness()
+    cap = 2 * n + 2
+    states = (C.c_uint64 * (cap * words))()
+    acts = (C.c_int32 * cap)()
+    ln = C.c_int32(0)
+    err = C.create_string_buffer(512)
+    rc = lib.tlcg_liveness_graph_selftest(c_row, c_col, c_p, n, n_init, words, C.byref(o), FAIRNESS[fairness],
+                                          C.byref(out), states, acts, cap, C.byref(ln), err, len(err))
+    if rc != 0:
+        raise RuntimeError(f"tlcg_liveness_graph_selftest: {rc}: {err.value.decode()}")
+    trace = [("Init" if acts[i] < 0 else acts[i], _from_words(states, i, words)) for i in range(ln.value)]
+    return Liveness(bool(out.holds), LIVE_KINDS[out.kind], fairness, out.depth, out.states_notp, out.init_notp,
+                    out.edges_notp, out.stuck, out.on_cycles, out.peel_rounds, trace, out.loop_to,
+                    out.back_action if out.loop_to >= 0 else None, out.kernel_ms, out.wall_ms)
 
 
 @dataclass

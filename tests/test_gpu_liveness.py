@@ -9,10 +9,17 @@ not-P states), its initial states and edges, the states where a behavior may
 stutter forever, and the depth of the shallowest one.  Which counterexample is
 printed is [TLC-ext]: the test checks that the returned one is a behavior of
 the spec that never reaches P and ends where the fairness allows stuttering."""
+import functools
+import json
+import subprocess
+
 import pytest
 
 import tlcgpu
-from conftest import GOLDEN, model_of
+from conftest import GOLDEN, ORACLE, model_of
+from liveness_ref import Reference, counts_of, model_graph
+from test_gpu_random_cfgs import random_model
+from test_gpu_tree import random_producer_model
 
 pytestmark = pytest.mark.gpu
 
@@ -102,3 +109,79 @@ def test_termination_g9_scaled():
            (16 ** 6 * per_state, 16 ** 6, 16 ** 6 * per_edge, 0, 0)
     print(f"G9 Termination under WF_vars(Next): {lv.states_notp} states, {lv.edges_notp} edges, "
           f"{lv.peel_rounds} peel rounds, kernels {lv.kernel_ms:.1f} ms, call {lv.wall_ms:.1f} ms")
+
+
+# ---- the model path against the plain reference (tests/liveness_ref.py) and
+# against the explicit-graph instantiation of the same kernels ----
+
+REF_CASES = ["D_N0_K1_nodeadlock", "R_C1_K2", "X_empty_spaces", "S", "S_consumer", "X_producer_sparse"]
+
+
+@functools.lru_cache(maxsize=None)
+def model_ref(case):
+    g, _ = model_graph(model_of(GOLDEN[case]["constants"]))
+    return Reference(g)
+
+
+@pytest.mark.parametrize("fair", ["none", "wf"])
+@pytest.mark.parametrize("case", REF_CASES)
+def test_termination_matches_reference(case, fair):
+    """depth (non-empty BFS levels), the Kahn rounds, what peeling leaves and
+    the stuck count are the reference's on the model's graph (model_graph),
+    like every other count; the same graph as CSR through
+    tlcg_liveness_graph_selftest -- the kernels' other instantiation -- gives
+    identical counts"""
+    ref = model_ref(case)
+    want = ref.counts(fair)
+    lv = tlcgpu.check_termination(model_of(GOLDEN[case]["constants"]), fair)
+    assert (lv.depth, lv.peel_rounds, lv.on_cycles, lv.stuck) == \
+           (want["depth"], want["peel_rounds"], want["on_cycles"], want["stuck"]), (case, fair)
+    assert counts_of(lv) == want, (case, fair)
+    g = ref.g
+    gv = tlcgpu.liveness_graph(g.row, g.col, g.is_p, g.n_init, fairness=fair)
+    assert counts_of(gv) == counts_of(lv), (case, fair)
+    assert len(gv.trace) == len(lv.trace)
+
+
+def oracle_liveness(m, fair):
+    out = subprocess.run([ORACLE] + m.oracle_args() + ["-liveness", fair], check=True, capture_output=True,
+                         text=True).stdout
+    return json.loads(out)
+
+
+@pytest.mark.parametrize("seed", range(20))
+@pytest.mark.parametrize("gen", [random_model, random_producer_model], ids=lambda f: f.__name__)
+def test_termination_random_cfg_matches_oracle(gen, seed):
+    """seeded random constant sets against tlc_oracle -liveness none|wf run live"""
+    m = gen(seed)
+    assert tlcgpu.check_model(m) is None
+    for fair in ("none", "wf"):
+        want = oracle_liveness(m, fair)
+        assert not want["error"]
+        lv = tlcgpu.check_termination(m, fair)
+        assert lv.holds == want["holds"], (seed, fair)
+        assert (lv.states_notp, lv.init_notp, lv.edges_notp, lv.stuck) == \
+               (want["states_notp"], want["init_notp"], want["edges_notp"], want["stuck"]), (seed, fair)
+        assert lv.on_cycles == 0 and want["cyclic_sccs"] == 0
+        if fair == "wf":
+            assert len(lv.trace) == want["stuck_min_depth"]
+        if not lv.holds:
+            check_counterexample(m, lv)
+
+
+@pytest.mark.parametrize("case", ["W_C12_k1", "X_producer_sparse"])
+def test_termination_regrows_wide_and_producer(case):
+    """the grow-and-redo path on two-word states and on a Producer's fan-out:
+    from a 100-state store and a 256-slot FPSet, the unforced run's result"""
+    m = model_of(GOLDEN[case]["constants"])
+    for fair in ("none", "wf"):
+        want = GOLDEN[case]["liveness"][fair]
+        full = tlcgpu.check_termination(m, fair)
+        lv = tlcgpu.check_termination(m, fair, state_capacity=100, log2_fpset_slots=8)
+        assert (lv.holds, lv.states_notp, lv.init_notp, lv.edges_notp, lv.stuck) == \
+               (want["holds"], want["states_notp"], want["init_notp"], want["edges_notp"], want["stuck"])
+        assert counts_of(lv) == counts_of(full)
+        # (the path's inner states depend on which parent won; its end and length do not)
+        assert len(lv.trace) == len(full.trace) and lv.trace[-1:] == full.trace[-1:]
+        if not lv.holds:
+            check_counterexample(m, lv)
