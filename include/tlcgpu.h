@@ -366,6 +366,91 @@ int tlcg_liveness_graph_selftest(const uint32_t* row, const uint32_t* col, const
                                  tlcg_liveness* out, uint64_t* states, int32_t* actions, int32_t cap, int32_t* len,
                                  char* err, int32_t err_cap);
 
+/* ---- liveness: properties the user defines, <>Q, []<>Q and P ~> Q ----
+ * <- TLC's liveness checker for a PROPERTY that is a definition of the module
+ * (or of tlcg_model.user_defs) whose body, outer parentheses stripped, is
+ *   TLCG_PROP_EVENTUALLY        <>(Q) or <>Name
+ *   TLCG_PROP_INFINITELY_OFTEN  []<>(Q) or []<>Name
+ *   TLCG_PROP_LEADS_TO          (P) ~> (Q) or [](P => <>(Q))
+ * with P and Q state predicates of the subset user invariants are written in
+ * (they may use the other definitions).  Refused, with a message naming the
+ * definition, the line and the construct, never checked approximately: <>[]Q,
+ * conjunctions and other combinations of temporal formulas, a <> whose operand
+ * is neither parenthesised nor a bare name running to the end of the formula,
+ * a top-level => or <=> beside ~>, a bulleted list containing a temporal
+ * operator, primes, ENABLED, WF_ / SF_.
+ *
+ * A behavior violates the property iff from some point on it stays in ~Q
+ * states, and that point is a seed: S = the initial states with ~Q
+ * (EVENTUALLY), every reachable state with ~Q (INFINITELY_OFTEN), every
+ * reachable state with P /\ ~Q (LEADS_TO).  G' = the states reachable from S
+ * through ~Q states, S included.  Verdicts are tlcg_check_termination's with
+ * S in Init's place:
+ *   TLCG_FAIR_NONE     fails iff S is not empty (every state of G' may stutter
+ *                      forever; stuck = |G'|);
+ *   TLCG_FAIR_WF_NEXT  fails iff G' holds a state with no non-stuttering
+ *                      successor, or a cycle of non-stuttering steps.
+ * lv holds G' figures as tlcg_check_termination defines them, with BFS levels
+ * counted from the seeds (states_notp = |G'|, init_notp = |S|, depth = levels
+ * of G').  The counterexample is the BFS path from Init to a seed
+ * (states[seed_at] is the seed), then the path inside G': [TLC-ext] without
+ * fairness the seed is the first one in the BFS order of the reachable states
+ * and the behavior stutters there; with fairness the end state is the least
+ * packed stuck state of the shallowest level of G' that has one, or the first
+ * cycle reached from the shallowest state left after peeling, and the seed is
+ * the one its G' path starts from.  The figures (reachable, seeds, |G'|, its
+ * edges, stuck states, peeling) are what the definitions give and are checked
+ * against the oracle's evaluation of P and Q; the choice among several
+ * counterexamples and classify_ms are [TLC-ext].  lv.kernel_ms is the device
+ * time of every phase (reach, classify, seed, sub-BFS, peeling).
+ *
+ * The pass: the BFS of the whole reachable graph (the kernels of
+ * tlcg_check_termination with no P), one classification of every stored state
+ * by the compiled P and Q on the device, then the sub-BFS, peeling and
+ * extraction over stored indices; no second FPSet or store.  An evaluation
+ * error of P or Q on a reachable state is an error, not a verdict: the call
+ * returns -7 with error_state set, the message naming the predicate, and the
+ * BFS path to that state in states[0..*len).  o->state_capacity /
+ * o->log2_fpset_slots size the buffers (grown on demand); at most 2^32 - 1
+ * reachable states.  Returns 0; -1 bad argument; -2 the property is refused
+ * (message in err); -3 bad model; < -3 device or evaluation errors. */
+enum { TLCG_PROP_EVENTUALLY = 0, TLCG_PROP_INFINITELY_OFTEN = 1, TLCG_PROP_LEADS_TO = 2 };
+typedef struct tlcg_property {
+  tlcg_liveness lv;     /* G' figures, as tlcg_check_termination defines them (states_notp = |G'|, init_notp = |S|) */
+  int32_t form;         /* TLCG_PROP_* */
+  int32_t seed_at;      /* index in the trace of the seed state; -1 when it holds */
+  uint64_t reachable;   /* states of phase 1 */
+  uint64_t seeds;       /* |S| */
+  int64_t error_state;  /* -1, else the store index of the first P/Q evaluation error */
+  double classify_ms;   /* device time of the classification kernel (a part of lv.kernel_ms) */
+} tlcg_property;
+int tlcg_check_property(const tlcg_model* m, const tlcg_opts* o, int32_t fairness, const char* name,
+                        tlcg_property* out, uint64_t* states, int32_t* actions, int32_t cap, int32_t* len,
+                        char* err, int32_t err_cap);
+/* Self-test of the property pass on a caller's CSR graph (as
+ * tlcg_liveness_graph_selftest: the spec's graph is acyclic for every cfg, so
+ * only this entry reaches the cycle verdict): the reach BFS, seeding, sub-BFS,
+ * peeling and extraction, with the class of node v taken from is_p[v] /
+ * is_q[v] instead of the device interpreter (is_p is ignored unless form is
+ * TLCG_PROP_LEADS_TO).  Nodes the initial ones do not reach are not states.
+ * Fills *out and the counterexample like tlcg_check_property; actions are
+ * edge ordinals.  Returns 0, -1 on a malformed graph or argument, < -1 on a
+ * device error. */
+int tlcg_property_graph_selftest(const uint32_t* row, const uint32_t* col, const uint8_t* is_p, const uint8_t* is_q,
+                                 uint32_t n, uint32_t n_init, int32_t words, const tlcg_opts* o, int32_t fairness,
+                                 int32_t form, tlcg_property* out, uint64_t* states, int32_t* actions, int32_t cap,
+                                 int32_t* len, char* err, int32_t err_cap);
+/* The front end alone, on the host (no GPU): the form of property `name`
+ * (0 with *form = TLCG_PROP_*), or < 0 with the refusal in err: -1 a formula
+ * outside the forms above or an operand outside the predicate subset, -2 a
+ * definition with no temporal operator (a state predicate), -3 no such
+ * definition or a bad model. */
+int tlcg_host_property_form(const tlcg_model* m, const char* name, int32_t* form, char* err, int32_t cap);
+/* P and Q of property `name` on n states (tlcg_state_words words each), by the
+ * host interpreter: out[i] = bit 0 P, bit 1 Q, bit 2 an evaluation error of
+ * either (P is TRUE for the forms without one).  0, or < 0 as above. */
+int tlcg_host_property_eval(const tlcg_model* m, const char* name, const uint64_t* states, uint64_t n, uint8_t* out);
+
 /* Enable xGMI peer access among devices 0..n-1 (one process driving contexts
  * on several devices, e.g. tlc-hip -gpus N).  Returns the pairs enabled. */
 int tlcg_peer_access(int32_t n);

@@ -703,6 +703,40 @@ int tlcg_host_check_invariants_batch(const tlcg_model* m, const uint64_t* states
   return 0;
 }
 
+int tlcg_host_property_form(const tlcg_model* m, const char* name, int32_t* form, char* err, int32_t cap) {
+  auto fail = [&](int rc, const std::string& e) {
+    if (err && cap > 0) std::snprintf(err, (size_t)cap, "%s", e.c_str());
+    return rc;
+  };
+  HostModel hm;
+  std::string e;
+  if (!m || !name || !form) return fail(-3, "null argument");
+  if (!build_model(*m, &hm, &e)) return fail(-3, e);
+  int f = 0;
+  const int rc = compile_property(*m, hm, name, &f, nullptr, &e);
+  if (rc) return fail(rc, e);
+  *form = f;
+  if (err && cap > 0) err[0] = 0;
+  return 0;
+}
+
+int tlcg_host_property_eval(const tlcg_model* m, const char* name, const uint64_t* states, uint64_t n, uint8_t* out) {
+  HostModel hm;
+  std::string e;
+  if (!m || !name || (n && (!states || !out)) || !build_model(*m, &hm, &e)) return -3;
+  const std::unique_ptr<UserProg> prog(new UserProg);
+  int f = 0;
+  const int rc = compile_property(*m, hm, name, &f, prog.get(), &e);
+  if (rc) return rc;
+  const int w = state_words(hm.L);
+  for (uint64_t i = 0; i < n; ++i) {
+    const u128 s = join_words(states + i * (uint64_t)w, w);
+    const int p = eval_user<u128>(hm.L, *prog, 0, s), q = eval_user<u128>(hm.L, *prog, 1, s);
+    out[i] = (uint8_t)((p == EV_TRUE ? 1 : 0) | (q == EV_TRUE ? 2 : 0) | (p == EV_ERROR || q == EV_ERROR ? 4 : 0));
+  }
+  return 0;
+}
+
 int tlcg_host_check_invariants(const tlcg_model* m, uint64_t state) {
   HostModel hm;
   std::string e;

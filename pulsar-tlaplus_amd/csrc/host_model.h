@@ -27,6 +27,16 @@ struct HostModel {
 bool compile_user_invariants(const tlcg_model& m, const HostModel& hm, const std::vector<std::string>& names,
                              UserProg* P, std::string* err);
 std::vector<std::string> user_def_names(const char* text);
+// The temporal front end (user_inv.cpp): classifies definition `name` of
+// m.user_defs as <>Q, []<>Q or P ~> Q (*form = TLCG_PROP_*) and compiles its
+// operands into *P, entry 0 = P (the constant TRUE for the forms without one),
+// entry 1 = Q; P == nullptr: the form alone (the operands are still compiled,
+// so that an accepted form is one the check takes).  0; -1 with a message
+// naming the definition, the line and the construct when the formula is
+// outside these forms; -2 when the body holds no temporal operator at all (a
+// state predicate); -3 when there is no such definition.
+int compile_property(const tlcg_model& m, const HostModel& hm, const std::string& name, int* form, UserProg* P,
+                     std::string* err);
 // The compiled user invariants as device code for the run-time specialized
 // kernels (user_inv.cpp; model.h tlcg_user_eval), one function per invariant.
 // With the layout: the per-component outcome tables of the invariants that

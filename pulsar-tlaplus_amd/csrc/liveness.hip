@@ -39,6 +39,10 @@
 // own); holds / fails, |G'|, its edge count and the shallowest stuck depth are
 // cross-checked with the oracle's Tarjan SCC restatement (oracle/tlc_oracle.c
 // -liveness).
+//
+// The second half of the file checks the properties a user defines -- <>Q,
+// []<>Q, P ~> Q over compiled state predicates -- with the same kernels for
+// the reachable graph and a seeded pass in index space (tlcg_check_property).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -46,6 +50,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -750,6 +755,597 @@ int run_explicit(const uint32_t* row, const uint32_t* col, const uint8_t* is_p, 
   return run_liveness(dg, hg, o, fair, out, tr, err);
 }
 
+// ---------------------------------------------------------------- user-defined properties
+// <>Q, []<>Q and P ~> Q over predicates the user defines (tlcgpu.h
+// tlcg_check_property).  A behavior violates such a property iff from a seed
+// state on it stays in ~Q states; S, the seeds, are the initial ~Q states, the
+// reachable ~Q states, or the reachable P /\ ~Q states, and G' is what S
+// reaches through ~Q states.  The verdicts are the ones above with S in
+// Init's place.  S is not known before the reachable states are, so the pass
+// is
+//   1. reach: the BFS above over the whole graph (ReachAll: no P), which
+//      leaves the FPSet, the store with parents, slot_of / gidx_of;
+//   2. classify (k_pp_classify): P and Q of every stored state, once, by the
+//      compiled program (user_inv.h) into a class byte; later kernels read
+//      the byte only;
+//   3. seed (k_pp_seed): the seeds' indices into `order`, their member bits;
+//   4. sub-BFS in index space (k_pp_expand per level of G'): a successor's
+//      index is gidx_of of its FPSet slot; a Q successor ends the path; every
+//      other one gets an in-edge and is claimed by an atomicOr on its member
+//      bit -- the lane that sets it appends the index to `order` and writes
+//      the G' parent.  No second FPSet, no second store;
+//   5. Kahn peeling over `order` with the per-index in-degree (k_pp_zero,
+//      k_pp_peel, k_pp_left);
+//   6. counterexample: the G' path (or the lasso) back to its root seed,
+//      behind the reach BFS path from Init to that seed.
+// Per reachable state beside the reach pass's buffers: class byte, member
+// bit, order entry, G' parent, two peel list entries: 21.1 B.  The in-degree
+// and stuck arrays of the reach pass are reused, indexed by stored index (the
+// FPSet has at least as many slots as states).
+
+// G without a P: every state is kept
+template <typename G>
+struct ReachAll {
+  using word = typename G::word;
+  G g;
+  TLCG_HDM u64 n_init() const { return g.n_init(); }
+  TLCG_HDM word init(u64 i) const { return g.init(i); }
+  TLCG_HDM bool is_p(word) const { return false; }
+  TLCG_HDM int moves_bound() const { return g.moves_bound(); }
+  TLCG_HDM int move(word s, int k, word* t, int* ord) const { return g.move(s, k, t, ord); }
+  TLCG_HDM int ord_bits() const { return g.ord_bits(); }
+  TLCG_HDM int action_of(int ord) const { return g.action_of(ord); }
+};
+
+enum PpClass { PC_P = 1, PC_Q = 2, PC_ERR = 4 };
+
+// the class of a state: by the compiled P (entry 0) and Q (entry 1) ...
+template <typename W>
+struct ProgClass {
+  Layout L;
+  const UserProg* prog;  // device memory
+  __device__ unsigned classify(W s) const {
+    const int p = eval_user<W>(L, *prog, 0, s), q = eval_user<W>(L, *prog, 1, s);
+    return (p == EV_TRUE ? PC_P : 0u) | (q == EV_TRUE ? PC_Q : 0u) | (p == EV_ERROR || q == EV_ERROR ? PC_ERR : 0u);
+  }
+};
+// ... or, for an explicit graph, by the caller's bytes per node (p null: P is TRUE)
+template <typename W>
+struct ByteClass {
+  const unsigned char *p, *q;  // device memory
+  __device__ unsigned classify(W s) const {
+    const uint32_t v = ExplicitGraph<W>::node_of(s);
+    return (!p || p[v] ? PC_P : 0u) | (q[v] ? PC_Q : 0u);
+  }
+};
+
+struct PpCtr {
+  unsigned long long n;      // states of G' (entries of `order`)
+  unsigned long long edges;  // non-stuttering edges into states of G'
+  unsigned long long stuck;  // stuck states of the level just expanded
+  unsigned long long next;   // entries appended to the next peel list
+  unsigned long long key_hi, key_lo, pick;  // least stuck state of a level, then its stored index
+  unsigned long long first_seed;            // least stored index of a seed
+  unsigned long long first_err;             // least stored index of a state where P or Q fails to evaluate
+  unsigned int flags;
+  unsigned int pad;
+};
+
+struct PpBufs {
+  unsigned char* cls;    // per stored state: PC_*
+  u32* member;           // bit per stored state: in G'
+  u32* order;            // G' in BFS order from the seeds: stored indices
+  u64* gparent;          // per stored state: G' parent index << ord_bits | ordinal, NO_PARENT for a seed
+  u32* indeg;            // per stored state: edges from states of G'
+  unsigned char* stuck;  // per stored state: fairness lets a behavior stutter here forever
+  u64 n_all;             // stored (reachable) states
+  PpCtr* ctr;
+};
+
+// the wave's least index among its lanes with `hit` (lanes hold ascending indices)
+__device__ __forceinline__ void wave_first(bool hit, u64 i, unsigned long long* least) {
+  const u64 wm = __ballot(hit);
+  if (wm && __lane_id() == __ffsll((long long)wm) - 1) atomicMin(least, (unsigned long long)i);
+}
+
+template <typename R, typename C>
+__global__ __launch_bounds__(LV_BLOCK) void k_pp_classify(LvBufs<R> B, C cl, PpBufs pp) {
+  const u64 n = pp.n_all, stride = (u64)gridDim.x * LV_BLOCK;
+  bool seen = false;  // (wave-uniform: later chunks hold larger indices)
+  for (u64 base = (u64)blockIdx.x * LV_BLOCK; base < n; base += stride) {
+    const u64 g = base + threadIdx.x;
+    unsigned c = 0;
+    if (g < n) {
+      c = cl.classify(B.store[g]);
+      pp.cls[g] = (unsigned char)c;
+    }
+    const bool bad = (c & PC_ERR) != 0;
+    if (!seen && __ballot(bad)) {
+      wave_first(bad, g, &pp.ctr->first_err);
+      seen = true;
+    }
+  }
+}
+
+// the seeds among stored states [0, b): ~Q, and P where the form has one
+__global__ __launch_bounds__(LV_BLOCK) void k_pp_seed(PpBufs pp, u64 b, int form) {
+  const u64 stride = (u64)gridDim.x * LV_BLOCK;
+  bool seen = false;
+  for (u64 base = (u64)blockIdx.x * LV_BLOCK; base < b; base += stride) {
+    const u64 g = base + threadIdx.x;
+    const unsigned c = g < b ? pp.cls[g] : (unsigned)PC_Q;
+    const bool seed = !(c & PC_Q) && (form != TLCG_PROP_LEADS_TO || (c & PC_P));
+    if (!seen && __ballot(seed)) {
+      wave_first(seed, g, &pp.ctr->first_seed);
+      seen = true;
+    }
+    u64 at = 0;
+    block_claim<1>(&seed, &at, &pp.ctr->n);
+    if (seed && at < pp.n_all) {  // (always: a stored index is claimed once)
+      pp.order[at] = (u32)g;
+      pp.gparent[g] = NO_PARENT;
+      atomicOr(&pp.member[g >> 5], 1u << (g & 31));
+    }
+  }
+}
+
+// one BFS level of G': order[a, b)
+template <typename R>
+__global__ __launch_bounds__(LV_BLOCK) void k_pp_expand(LvBufs<R> B, PpBufs pp, u64 a, u64 b, int fair) {
+  using W = typename R::word;
+  const R& gr = B.g;
+  const int kmax = gr.moves_bound(), ord_bits = gr.ord_bits();
+  const u64 stride = (u64)gridDim.x * LV_BLOCK;
+  u64 edges = 0, nstuck = 0;
+  bool err = false, lost = false;
+  for (u64 base = a + (u64)blockIdx.x * LV_BLOCK; base < b; base += stride) {
+    const u64 i = base + threadIdx.x;
+    const bool live = i < b;
+    const u64 g = live ? pp.order[i] : 0;
+    const W s = live ? B.store[g] : (W)0;
+    int moves = 0;
+    for (int k0 = 0; k0 < kmax; k0 += LV_BATCH) {
+      W t[LV_BATCH];
+      int ord[LV_BATCH];
+      bool want[LV_BATCH], fresh[LV_BATCH];
+      u64 slot[LV_BATCH];
+      u32 tg[LV_BATCH];
+#pragma unroll
+      for (int j = 0; j < LV_BATCH; ++j) {
+        t[j] = 0;
+        ord[j] = 0;
+        const int r = live && k0 + j < kmax ? gr.move(s, k0 + j, &t[j], &ord[j]) : 0;
+        err |= r == 2;
+        moves += r == 1;
+        want[j] = r == 1;
+      }
+      lv_lookup_batch(B, want, t, slot);
+#pragma unroll
+      for (int j = 0; j < LV_BATCH; ++j) {
+        fresh[j] = false;
+        tg[j] = 0;
+        if (!want[j]) continue;
+        const u32 x = slot[j] == ~0ull ? ~0u : B.gidx_of[slot[j]];
+        if (x >= pp.n_all) {  // (every successor of a stored state is stored)
+          lost = true;
+          continue;
+        }
+        if (pp.cls[x] & PC_Q) continue;  // a Q state ends the path
+        ++edges;
+        atomicAdd(&pp.indeg[x], 1u);
+        const u32 bit = 1u << (x & 31);
+        fresh[j] = !(atomicOr(&pp.member[x >> 5], bit) & bit);
+        tg[j] = x;
+      }
+      u64 ats[LV_BATCH];
+      block_claim<LV_BATCH>(fresh, ats, &pp.ctr->n);
+#pragma unroll
+      for (int j = 0; j < LV_BATCH; ++j)
+        if (fresh[j]) {
+          if (ats[j] >= pp.n_all) {
+            lost = true;
+          } else {
+            pp.order[ats[j]] = tg[j];
+            pp.gparent[tg[j]] = (g << ord_bits) | (u64)ord[j];
+          }
+        }
+    }
+    const bool stuck = live && (fair == TLCG_FAIR_NONE || moves == 0);
+    if (live) pp.stuck[g] = stuck;
+    nstuck += stuck;
+  }
+  if (err) atomicOr(&pp.ctr->flags, (unsigned)LV_EVAL);
+  if (lost) atomicOr(&pp.ctr->flags, (unsigned)LV_LOOKUP);
+  const u64 e = wave_sum_u64(edges), sk = wave_sum_u64(nstuck);
+  if (__lane_id() == 0) {
+    if (e) atomicAdd(&pp.ctr->edges, (unsigned long long)e);
+    if (sk) atomicAdd(&pp.ctr->stuck, (unsigned long long)sk);
+  }
+}
+
+// the least stuck state of level order[a, b), as k_lv_pick
+template <typename R>
+__global__ __launch_bounds__(LV_BLOCK) void k_pp_pick(LvBufs<R> B, PpBufs pp, u64 a, u64 b, int phase) {
+  using W = typename R::word;
+  const u64 stride = (u64)gridDim.x * LV_BLOCK;
+  for (u64 i = a + (u64)blockIdx.x * LV_BLOCK + threadIdx.x; i < b; i += stride) {
+    const u64 g = pp.order[i];
+    if (!pp.stuck[g]) continue;
+    const W s = B.store[g];
+    const u64 hi = sizeof(W) == 8 ? 0 : (u64)((unsigned __int128)s >> 64), lo = (u64)s;
+    if (phase == 0) atomicMin(&pp.ctr->key_hi, (unsigned long long)hi);
+    else if (phase == 1) { if (hi == pp.ctr->key_hi) atomicMin(&pp.ctr->key_lo, (unsigned long long)lo); }
+    else if (hi == pp.ctr->key_hi && lo == pp.ctr->key_lo) pp.ctr->pick = g;
+  }
+}
+
+// Kahn peeling over G': the states of in-degree 0 (stored indices), or with
+// left = 1 the ones that kept an in-edge (positions in `order`: G' BFS order)
+__global__ __launch_bounds__(LV_BLOCK) void k_pp_zero(PpBufs pp, u64 n, u32* list, int left) {
+  const u64 stride = (u64)gridDim.x * LV_BLOCK;
+  for (u64 base = (u64)blockIdx.x * LV_BLOCK; base < n; base += stride) {
+    const u64 i = base + threadIdx.x;
+    const u32 g = i < n ? pp.order[i] : 0;
+    const bool z = i < n && (pp.indeg[g] == 0) != (left != 0);
+    u64 at = 0;
+    block_claim<1>(&z, &at, &pp.ctr->next);
+    if (z) list[at] = left ? (u32)i : g;
+  }
+}
+
+template <typename R>
+__global__ __launch_bounds__(LV_BLOCK) void k_pp_peel(LvBufs<R> B, PpBufs pp, const u32* list, u64 n, u32* next) {
+  using W = typename R::word;
+  const R& gr = B.g;
+  const int kmax = gr.moves_bound();
+  const u64 stride = (u64)gridDim.x * LV_BLOCK;
+  bool lost = false;
+  for (u64 base = (u64)blockIdx.x * LV_BLOCK; base < n; base += stride) {
+    const u64 i = base + threadIdx.x;
+    const bool live = i < n;
+    const W s = live ? B.store[list[i]] : (W)0;
+    for (int k0 = 0; k0 < kmax; k0 += LV_BATCH) {
+      W t[LV_BATCH];
+      bool want[LV_BATCH], freed[LV_BATCH];
+      u64 slot[LV_BATCH];
+      u32 tg[LV_BATCH];
+#pragma unroll
+      for (int j = 0; j < LV_BATCH; ++j) {
+        t[j] = 0;
+        int ord = 0;
+        want[j] = live && k0 + j < kmax && gr.move(s, k0 + j, &t[j], &ord) == 1;
+      }
+      lv_lookup_batch(B, want, t, slot);
+#pragma unroll
+      for (int j = 0; j < LV_BATCH; ++j) {
+        freed[j] = false;
+        tg[j] = 0;
+        if (!want[j]) continue;
+        const u32 x = slot[j] == ~0ull ? ~0u : B.gidx_of[slot[j]];
+        if (x >= pp.n_all) {
+          lost = true;
+          continue;
+        }
+        if (pp.cls[x] & PC_Q) continue;
+        // (a not-Q successor of a state of G' is in G': the sub-BFS counted this edge)
+        if (atomicSub(&pp.indeg[x], 1u) == 1u) {
+          freed[j] = true;
+          tg[j] = x;
+        }
+      }
+      u64 ats[LV_BATCH];
+      block_claim<LV_BATCH>(freed, ats, &pp.ctr->next);
+#pragma unroll
+      for (int j = 0; j < LV_BATCH; ++j)
+        if (freed[j]) {
+          if (ats[j] >= pp.n_all) lost = true;
+          else next[ats[j]] = tg[j];
+        }
+    }
+  }
+  if (lost) atomicOr(&pp.ctr->flags, (unsigned)LV_LOOKUP);
+}
+
+// the states at positions pos[0 .. n) of `order` (checked by the host to lie inside it)
+template <typename R>
+__global__ __launch_bounds__(LV_BLOCK) void k_pp_gather(LvBufs<R> B, PpBufs pp, const u32* pos, u64 n,
+                                                        typename R::word* out) {
+  const u64 stride = (u64)gridDim.x * LV_BLOCK;
+  for (u64 i = (u64)blockIdx.x * LV_BLOCK + threadIdx.x; i < n; i += stride) out[i] = B.store[pp.order[pos[i]]];
+}
+
+// The path inside G' from its root seed to stored state g, behind the reach
+// BFS path from Init to that seed; *seed_at = the seed's place in the trace
+template <typename R>
+int pp_path(const LvBufs<R>& B, const PpBufs& pp, const R& hg, u64 g, LvTrace* tr, int* seed_at, std::string* err) {
+  using W = typename R::word;
+  const int ord_bits = hg.ord_bits();
+  std::vector<std::pair<u64, u64>> rev;  // (stored index, G' parent reference)
+  for (;;) {
+    u64 p;
+    LV_CHECK(hipMemcpy(&p, pp.gparent + g, sizeof(u64), hipMemcpyDeviceToHost));
+    rev.push_back({g, p});
+    if (p == NO_PARENT || rev.size() > 1u << 20) break;
+    g = p >> ord_bits;
+    if (g >= pp.n_all) {
+      *err = "property: a G' parent reference leaves the store";
+      return -6;
+    }
+  }
+  if (const int rc = path_to(B, hg, rev.back().first, tr, err)) return rc;
+  *seed_at = (int)tr->states.size() - 1;
+  for (size_t i = rev.size() - 1; i-- > 0;) {
+    W s;
+    LV_CHECK(hipMemcpy(&s, B.store + rev[i].first, sizeof(W), hipMemcpyDeviceToHost));
+    tr->states.push_back((u128)s);
+    tr->actions.push_back(hg.action_of((int)(rev[i].second & ((1ull << ord_bits) - 1))));
+  }
+  return 0;
+}
+
+// dg / hg: the graph as the kernels / the host read it, cl: the classifier
+// (device memory behind it).  -7: P or Q failed to evaluate on stored state
+// out->error_state, *tr the BFS path to it.
+template <typename G, typename C>
+int run_property(const G& dg0, const G& hg0, const C& cl, const tlcg_opts* o, int fair, int form, tlcg_property* out,
+                 LvTrace* tr, std::string* err) {
+  using R = ReachAll<G>;
+  using W = typename G::word;
+  const R dg{dg0}, hg{hg0};
+  const unsigned grid_cap = lv_grid_cap();
+  auto grid_for = [grid_cap](u64 n) { return lv_grid(n, grid_cap); };
+  u64 cap = o && o->state_capacity ? o->state_capacity : (u64)1 << 22;
+  int log2 = o && o->log2_fpset_slots > 0 ? o->log2_fpset_slots : 0;
+  hipEvent_t e0, e1;
+  LV_CHECK(hipEventCreate(&e0));
+  LV_CHECK(hipEventCreate(&e1));
+  struct EvGuard {
+    hipEvent_t a, b;
+    ~EvGuard() {
+      hipEventDestroy(a);
+      hipEventDestroy(b);
+    }
+  } evg{e0, e1};
+  tlcg_liveness* lv = &out->lv;
+  for (int attempt = 0;; ++attempt) {
+    if (cap >= (1ull << 32) - 1) {
+      *err = "the property check indexes states with 32 bits: more than 2^32 - 1 reachable states";
+      return -5;
+    }
+    int lg = log2;
+    if (lg <= 0 || attempt > 0) {
+      lg = 10;
+      while ((1ull << lg) < 2 * cap) ++lg;
+    }
+    if (lg > 32) lg = 32;
+    DevMem mem;
+    LvBufs<R> B;
+    B.g = dg;
+    B.log2 = lg;
+    B.cap = cap;
+    const u64 nslots = 1ull << lg;
+    PpBufs pp{};
+    // 1. reach (the peel lists and G' arrays are sized by the capacity, so that
+    // what does not fit is known before the BFS, not after it)
+    u32 *la = nullptr, *lb = nullptr;
+    if (!mem.alloc(&B.slots, nslots * (sizeof(W) / 8)) || !mem.alloc(&B.store, cap) || !mem.alloc(&B.parent, cap) ||
+        !mem.alloc(&B.slot_of, cap) || !mem.alloc(&B.gidx_of, nslots) || !mem.alloc(&B.indeg, nslots) ||
+        !mem.alloc(&B.stuck, cap) || !mem.alloc(&B.ctr, 1) || !mem.alloc(&pp.cls, cap) ||
+        !mem.alloc(&pp.member, cap / 32 + 1) || !mem.alloc(&pp.order, cap) || !mem.alloc(&pp.gparent, cap) ||
+        !mem.alloc(&la, cap) || !mem.alloc(&lb, cap) || !mem.alloc(&pp.ctr, 1)) {
+      if (cap > (1ull << 20) && attempt < 8) {
+        cap /= 2;
+        log2 = 0;
+        continue;
+      }
+      *err = "property: device allocation failed (" + std::to_string(cap) + " states, 2^" + std::to_string(lg) +
+             " FPSet slots)";
+      return -5;
+    }
+    LV_CHECK(hipMemset(B.slots, 0, nslots * sizeof(W)));
+    LV_CHECK(hipMemset(B.indeg, 0, nslots * sizeof(u32)));
+    LvCtr h{};
+    h.first_init = ~0ull;
+    LV_CHECK(hipMemcpy(B.ctr, &h, sizeof h, hipMemcpyHostToDevice));
+    auto read_ctr = [&]() -> int {
+      LV_CHECK(hipMemcpy(&h, B.ctr, sizeof h, hipMemcpyDeviceToHost));
+      return 0;
+    };
+    float ms_total = 0.f, ms = 0.f;
+    LV_CHECK(hipEventRecord(e0, 0));
+    k_lv_init<R><<<grid_for(hg.n_init()), LV_BLOCK>>>(B);
+    LV_CHECK(hipGetLastError());
+    if (read_ctr()) return -4;
+    std::vector<u64> level_base{0, std::min<u64>(h.n, cap)};
+    bool again = (h.flags & (LV_FPSET | LV_STORE)) != 0;
+    while (!again && level_base.back() > level_base[level_base.size() - 2]) {
+      const u64 a = level_base[level_base.size() - 2], b = level_base.back();
+      k_lv_expand<R><<<grid_for(b - a), LV_BLOCK>>>(B, a, b, fair);
+      LV_CHECK(hipGetLastError());
+      if (read_ctr()) return -4;
+      if (h.flags & LV_EVAL) {
+        *err = "property: an evaluation error while computing a successor (run the safety check first)";
+        return -6;
+      }
+      if ((again = (h.flags & (LV_FPSET | LV_STORE)) != 0)) break;
+      level_base.push_back(h.n);
+    }
+    LV_CHECK(hipEventRecord(e1, 0));
+    LV_CHECK(hipEventSynchronize(e1));
+    LV_CHECK(hipEventElapsedTime(&ms, e0, e1));
+    ms_total += ms;
+    if (again) {
+      cap *= 4;
+      continue;  // redo with a larger store and FPSet
+    }
+    const u64 n_all = h.n;
+    out->reachable = n_all;
+    // 2. classify
+    pp.indeg = B.indeg;  // (nslots >= n_all entries; by stored index from here on)
+    pp.stuck = B.stuck;
+    pp.n_all = n_all;
+    PpCtr c{};
+    c.first_seed = c.first_err = ~0ull;
+    LV_CHECK(hipMemcpy(pp.ctr, &c, sizeof c, hipMemcpyHostToDevice));
+    auto read_pp = [&]() -> int {
+      LV_CHECK(hipMemcpy(&c, pp.ctr, sizeof c, hipMemcpyDeviceToHost));
+      return 0;
+    };
+    LV_CHECK(hipMemset(pp.indeg, 0, n_all * sizeof(u32)));
+    LV_CHECK(hipMemset(pp.stuck, 0, n_all));
+    LV_CHECK(hipMemset(pp.member, 0, (n_all / 32 + 1) * sizeof(u32)));
+    LV_CHECK(hipEventRecord(e0, 0));
+    k_pp_classify<R, C><<<grid_for(n_all), LV_BLOCK>>>(B, cl, pp);
+    LV_CHECK(hipGetLastError());
+    LV_CHECK(hipEventRecord(e1, 0));
+    LV_CHECK(hipEventSynchronize(e1));
+    LV_CHECK(hipEventElapsedTime(&ms, e0, e1));
+    out->classify_ms = ms;
+    ms_total += ms;
+    if (read_pp()) return -4;
+    if (c.first_err != ~0ull) {
+      out->error_state = (int64_t)c.first_err;
+      lv->kernel_ms = ms_total;
+      if (const int rc = path_to(B, hg, c.first_err, tr, err)) return rc;
+      *err = "property: P or Q failed to evaluate on a reachable state";
+      return -7;
+    }
+    // 3. seed, 4. sub-BFS
+    LV_CHECK(hipEventRecord(e0, 0));
+    const u64 seed_range = form == TLCG_PROP_EVENTUALLY ? level_base[1] : n_all;
+    k_pp_seed<<<grid_for(seed_range), LV_BLOCK>>>(pp, seed_range, form);
+    LV_CHECK(hipGetLastError());
+    if (read_pp()) return -4;
+    out->seeds = c.n;
+    std::vector<u64> glevel{0, c.n}, level_stuck;
+    while (glevel.back() > glevel[glevel.size() - 2]) {
+      const u64 a = glevel[glevel.size() - 2], b = glevel.back();
+      LV_CHECK(hipMemset(&pp.ctr->stuck, 0, sizeof(unsigned long long)));
+      k_pp_expand<R><<<grid_for(b - a), LV_BLOCK>>>(B, pp, a, b, fair);
+      LV_CHECK(hipGetLastError());
+      if (read_pp()) return -4;
+      if (c.flags & (LV_EVAL | LV_LOOKUP)) {
+        *err = "property: a successor of a reachable state is missing from the FPSet";
+        return -6;
+      }
+      level_stuck.push_back(c.stuck);
+      glevel.push_back(c.n);
+    }
+    const u64 n = c.n;
+    lv->states_notp = n;
+    lv->init_notp = out->seeds;
+    lv->edges_notp = c.edges;
+    lv->depth = (int32_t)(glevel.size() - 2);
+    lv->stuck = 0;
+    for (u64 x : level_stuck) lv->stuck += x;
+    // 5. Kahn peeling
+    LV_CHECK(hipMemset(&pp.ctr->next, 0, sizeof(unsigned long long)));
+    k_pp_zero<<<grid_for(n), LV_BLOCK>>>(pp, n, la, 0);
+    LV_CHECK(hipGetLastError());
+    if (read_pp()) return -4;
+    u64 removed = 0, cur = c.next;
+    int rounds = 0;
+    while (cur) {
+      removed += cur;
+      ++rounds;
+      LV_CHECK(hipMemset(&pp.ctr->next, 0, sizeof(unsigned long long)));
+      k_pp_peel<R><<<grid_for(cur), LV_BLOCK>>>(B, pp, la, cur, lb);
+      LV_CHECK(hipGetLastError());
+      if (read_pp()) return -4;
+      if (c.flags & LV_LOOKUP) {
+        *err = "property: a successor in G' is missing from the FPSet";
+        return -6;
+      }
+      cur = c.next;
+      std::swap(la, lb);
+    }
+    LV_CHECK(hipEventRecord(e1, 0));
+    LV_CHECK(hipEventSynchronize(e1));
+    LV_CHECK(hipEventElapsedTime(&ms, e0, e1));
+    ms_total += ms;
+    lv->peel_rounds = rounds;
+    lv->on_cycles = n - removed;
+    lv->kernel_ms = ms_total;
+    // 6. verdict and counterexample
+    if (lv->stuck && fair == TLCG_FAIR_NONE) {
+      // every state of G' may stutter forever: the first seed in the BFS order
+      // of the reachable states, then stuttering
+      lv->holds = 0;
+      lv->kind = TLCG_LIVE_STUTTERING;
+      if (const int rc = path_to(B, hg, c.first_seed, tr, err)) return rc;
+      out->seed_at = (int)tr->states.size() - 1;
+      return 0;
+    }
+    if (lv->stuck) {
+      lv->holds = 0;
+      lv->kind = TLCG_LIVE_STUTTERING;
+      size_t l = 0;
+      while (level_stuck[l] == 0) ++l;
+      const u64 a = glevel[l], b = glevel[l + 1];
+      c.key_hi = c.key_lo = ~0ull;
+      c.pick = ~0ull;
+      LV_CHECK(hipMemcpy(pp.ctr, &c, sizeof c, hipMemcpyHostToDevice));
+      for (int ph = 0; ph < 3; ++ph) k_pp_pick<R><<<grid_for(b - a), LV_BLOCK>>>(B, pp, a, b, ph);
+      LV_CHECK(hipGetLastError());
+      if (read_pp()) return -4;
+      if (c.pick >= n_all) {
+        *err = "property: no stuck state found in its level";
+        return -6;
+      }
+      return pp_path(B, pp, hg, c.pick, tr, &out->seed_at, err);
+    }
+    if (removed == n) {
+      lv->holds = 1;
+      lv->kind = TLCG_LIVE_HOLDS;
+      return 0;
+    }
+    // a cycle: the states left after peeling, by their place in G' BFS order
+    lv->holds = 0;
+    lv->kind = TLCG_LIVE_CYCLE;
+    const u64 left = n - removed;
+    if (left > (1ull << 26)) {
+      *err = "property: " + std::to_string(left) + " states lie on or after cycles; the lasso extraction takes at most 2^26";
+      return -5;
+    }
+    LV_CHECK(hipMemset(&pp.ctr->next, 0, sizeof(unsigned long long)));
+    k_pp_zero<<<grid_for(n), LV_BLOCK>>>(pp, n, la, 1);
+    LV_CHECK(hipGetLastError());
+    std::vector<u32> pos(left), ord_h(n);
+    std::vector<W> st(left);
+    LV_CHECK(hipMemcpy(pos.data(), la, left * sizeof(u32), hipMemcpyDeviceToHost));
+    LV_CHECK(hipMemcpy(ord_h.data(), pp.order, n * sizeof(u32), hipMemcpyDeviceToHost));
+    std::sort(pos.begin(), pos.end());
+    for (u64 i = 0; i < left; ++i)
+      if (pos[i] >= n || ord_h[pos[i]] >= n_all) {
+        *err = "property: a state left after peeling lies outside G'";
+        return -6;
+      }
+    // their states, gathered on the device in that order and copied at once
+    W* d_st = nullptr;
+    if (!mem.alloc(&d_st, left)) {
+      *err = "property: device allocation failed (the states left after peeling)";
+      return -5;
+    }
+    LV_CHECK(hipMemcpy(la, pos.data(), left * sizeof(u32), hipMemcpyHostToDevice));
+    k_pp_gather<R><<<grid_for(left), LV_BLOCK>>>(B, pp, la, left, d_st);
+    LV_CHECK(hipGetLastError());
+    LV_CHECK(hipMemcpy(st.data(), d_st, left * sizeof(W), hipMemcpyDeviceToHost));
+    // (the walk stays among the states left, none of which satisfies Q, so the
+    // host graph needs no Q of its own)
+    u64 p_entry = 0;
+    std::vector<u128> cyc;
+    std::vector<int> cyc_act;
+    int back = -1;
+    if (lasso_walk(hg, st, pos, &p_entry, &cyc, &cyc_act, &back, err) != 0) return -6;
+    if (const int rc = pp_path(B, pp, hg, ord_h[p_entry], tr, &out->seed_at, err)) return rc;
+    tr->loop_to = (int)tr->states.size() - 1;
+    tr->states.insert(tr->states.end(), cyc.begin(), cyc.end());
+    tr->actions.insert(tr->actions.end(), cyc_act.begin(), cyc_act.end());
+    tr->back_action = back;
+    return 0;
+  }
+}
+
 }  // namespace
 
 extern "C" int tlcg_check_termination(const tlcg_model* m, const tlcg_opts* o, int32_t fairness, tlcg_liveness* out,
@@ -807,5 +1403,139 @@ extern "C" int tlcg_liveness_graph_selftest(const uint32_t* row, const uint32_t*
   out->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (rc) return fail(rc, e);
   lv_copy_out(tr, words, out, states, actions, cap, len);
+  return 0;
+}
+
+namespace {
+
+void pp_copy_out(const LvTrace& tr, int words, tlcg_property* out, uint64_t* states, int32_t* actions, int32_t cap,
+                 int32_t* len) {
+  lv_copy_out(tr, words, &out->lv, states, actions, cap, len);
+}
+
+template <typename W>
+int run_model_property(const HostModel& hm, const UserProg* d_prog, const tlcg_opts* o, int fair, int form,
+                       tlcg_property* out, LvTrace* tr, std::string* err) {
+  ModelGraph<W> g;
+  g.L = hm.L;
+  g.n_init_ = hm.n_init;
+  const ProgClass<W> cl{hm.L, d_prog};
+  return run_property(g, g, cl, o, fair, form, out, tr, err);
+}
+
+template <typename W>
+int run_explicit_property(const uint32_t* row, const uint32_t* col, const uint8_t* is_p, const uint8_t* is_q,
+                          uint32_t n, uint32_t n_init, const tlcg_opts* o, int fair, int form, tlcg_property* out,
+                          LvTrace* tr, std::string* err) {
+  ExplicitGraph<W> hg{};
+  if (!explicit_graph_shape(row, col, n, n_init, &hg, err)) return -1;
+  hg.row = row;
+  hg.col = col;
+  hg.p = nullptr;  // (ReachAll asks for no P)
+  DevMem mem;
+  uint32_t *d_row = nullptr, *d_col = nullptr;
+  unsigned char *d_p = nullptr, *d_q = nullptr;
+  if (!mem.alloc(&d_row, (u64)n + 1) || !mem.alloc(&d_col, row[n]) || !mem.alloc(&d_p, n) || !mem.alloc(&d_q, n)) {
+    *err = "graph: device allocation failed";
+    return -5;
+  }
+  LV_CHECK(hipMemcpy(d_row, row, ((size_t)n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
+  if (row[n]) LV_CHECK(hipMemcpy(d_col, col, (size_t)row[n] * sizeof(uint32_t), hipMemcpyHostToDevice));
+  const bool has_p = form == TLCG_PROP_LEADS_TO;
+  if (n && has_p) LV_CHECK(hipMemcpy(d_p, is_p, n, hipMemcpyHostToDevice));
+  if (n) LV_CHECK(hipMemcpy(d_q, is_q, n, hipMemcpyHostToDevice));
+  ExplicitGraph<W> dg = hg;
+  dg.row = d_row;
+  dg.col = d_col;
+  const ByteClass<W> cl{has_p ? d_p : nullptr, d_q};
+  return run_property(dg, hg, cl, o, fair, form, out, tr, err);
+}
+
+void pp_reset(tlcg_property* out, int fairness, int form) {
+  std::memset(out, 0, sizeof *out);
+  out->lv.fairness = fairness;
+  out->lv.loop_to = -1;
+  out->form = form;
+  out->seed_at = -1;
+  out->error_state = -1;
+}
+
+}  // namespace
+
+extern "C" int tlcg_check_property(const tlcg_model* m, const tlcg_opts* o, int32_t fairness, const char* name,
+                                   tlcg_property* out, uint64_t* states, int32_t* actions, int32_t cap, int32_t* len,
+                                   char* err, int32_t err_cap) {
+  auto fail = [&](int rc, const std::string& e) {
+    if (err && err_cap > 0) std::snprintf(err, (size_t)err_cap, "%s", e.c_str());
+    return rc;
+  };
+  if (!m || !out || !name) return fail(-1, "null argument");
+  if (fairness != TLCG_FAIR_NONE && fairness != TLCG_FAIR_WF_NEXT) return fail(-1, "unknown fairness");
+  pp_reset(out, fairness, 0);
+  if (len) *len = 0;
+  HostModel hm;
+  std::string e;
+  if (!build_model(*m, &hm, &e)) return fail(-3, e);
+  const std::unique_ptr<UserProg> prog(new UserProg);
+  int form = 0;
+  if (compile_property(*m, hm, name, &form, prog.get(), &e) != 0) return fail(-2, e);
+  out->form = form;
+  if (hipSetDevice(o ? o->device : 0) != hipSuccess) return fail(-4, "hipSetDevice failed");
+  const auto t0 = std::chrono::steady_clock::now();
+  DevMem mem;
+  UserProg* d_prog = nullptr;
+  if (!mem.alloc(&d_prog, 1) ||
+      hipMemcpy(d_prog, prog.get(), sizeof(UserProg), hipMemcpyHostToDevice) != hipSuccess)
+    return fail(-5, "property: device allocation failed (the predicates' program)");
+  LvTrace tr;
+  const int words = state_words(hm.L);
+  const int rc = words == 1 ? run_model_property<u64>(hm, d_prog, o, fairness, form, out, &tr, &e)
+                            : run_model_property<u128>(hm, d_prog, o, fairness, form, out, &tr, &e);
+  out->lv.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (rc == -7 && !tr.states.empty()) {
+    // which predicate: the host interpreter on the same state
+    const u128 s = tr.states.back();
+    const bool p_err = eval_user<u128>(hm.L, *prog, 0, s) == EV_ERROR;
+    e = std::string("evaluating ") + (p_err ? "P (the left operand)" : "Q") + " of property " + name +
+        " failed on a reachable state (the last state of the trace)";
+    pp_copy_out(tr, words, out, states, actions, cap, len);
+    return fail(rc, e);
+  }
+  if (rc) return fail(rc, e);
+  pp_copy_out(tr, words, out, states, actions, cap, len);
+  return 0;
+}
+
+extern "C" int tlcg_property_graph_selftest(const uint32_t* row, const uint32_t* col, const uint8_t* is_p,
+                                            const uint8_t* is_q, uint32_t n, uint32_t n_init, int32_t words,
+                                            const tlcg_opts* o, int32_t fairness, int32_t form, tlcg_property* out,
+                                            uint64_t* states, int32_t* actions, int32_t cap, int32_t* len, char* err,
+                                            int32_t err_cap) {
+  auto fail = [&](int rc, const std::string& e) {
+    if (err && err_cap > 0) std::snprintf(err, (size_t)err_cap, "%s", e.c_str());
+    return rc;
+  };
+  if (form != TLCG_PROP_EVENTUALLY && form != TLCG_PROP_INFINITELY_OFTEN && form != TLCG_PROP_LEADS_TO)
+    return fail(-1, "unknown form");
+  if (!row || !out || (n && (!is_q || (form == TLCG_PROP_LEADS_TO && !is_p)))) return fail(-1, "null argument");
+  if (fairness != TLCG_FAIR_NONE && fairness != TLCG_FAIR_WF_NEXT) return fail(-1, "unknown fairness");
+  if (words != 1 && words != 2) return fail(-1, "words must be 1 or 2");
+  if (row[n] && !col) return fail(-1, "null argument");
+  pp_reset(out, fairness, form);
+  if (len) *len = 0;
+  std::string e;
+  {  // a malformed graph is refused before the device is touched
+    ExplicitGraph<u64> shape{};
+    if (!explicit_graph_shape(row, col, n, n_init, &shape, &e)) return fail(-1, e);
+  }
+  if (hipSetDevice(o ? o->device : 0) != hipSuccess) return fail(-4, "hipSetDevice failed");
+  const auto t0 = std::chrono::steady_clock::now();
+  LvTrace tr;
+  const int rc = words == 1
+                     ? run_explicit_property<u64>(row, col, is_p, is_q, n, n_init, o, fairness, form, out, &tr, &e)
+                     : run_explicit_property<u128>(row, col, is_p, is_q, n, n_init, o, fairness, form, out, &tr, &e);
+  out->lv.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (rc) return fail(rc, e);
+  pp_copy_out(tr, words, out, states, actions, cap, len);
   return 0;
 }

@@ -59,6 +59,7 @@ struct Tok {
   std::string s;
   long long v = 0;
   int line = 0, col = 0;
+  size_t off = 0, end = 0;  // the token's extent in the text
 };
 
 std::vector<Tok> lex(const std::string& text, int line0) {
@@ -105,6 +106,7 @@ std::vector<Tok> lex(const std::string& text, int line0) {
     Tok t;
     t.line = line;
     t.col = col;
+    t.off = i;
     if (std::isalpha((unsigned char)ch) || ch == '_') {
       size_t j = i;
       while (j < text.size() && (std::isalnum((unsigned char)text[j]) || text[j] == '_')) ++j;
@@ -147,6 +149,7 @@ std::vector<Tok> lex(const std::string& text, int line0) {
         adv(1);
       }
     }
+    t.end = i;
     out.push_back(t);
   }
   Tok e;
@@ -686,12 +689,22 @@ class Compiler {
     auto it = defs.find(name);
     if (it == defs.end()) throw CompileError("invariant " + name + " is not defined");
     if (!it->second.params.empty()) throw CompileError("invariant " + name + " takes arguments");
+    compile_def(k, it->second, "invariant " + name);
+  }
+  // compiles the body of d (a definition, or a part of one: a property's P or Q) as entry k
+  void compile_def(int k, Def& d, const std::string& what, const std::string& at = std::string()) {
     P_->entry[k] = pc();
     nreg_ = 0;
     EnvP env = std::make_shared<Env>();
-    const Val v = lower(body_of(it->second), env);
-    if (v.t != T_BOOL) throw CompileError("invariant " + name + " is a " + tk_name(v.t) + ", not a boolean");
+    const Val v = lower(body_of(d), env);
+    if (v.t != T_BOOL) throw CompileError(what + " is a " + tk_name(v.t) + ", not a boolean" + at);
     emit(U_RET, v.r[0]);
+  }
+  // entry k = the constant TRUE
+  void compile_true(int k) {
+    P_->entry[k] = pc();
+    nreg_ = 0;
+    emit(U_RET, ldi(1));
   }
 
  private:
@@ -2028,13 +2041,8 @@ std::vector<Def> split_defs(const std::string& text) {
   return out;
 }
 
-}  // namespace
-
-// Compiles the user invariants of a model (the definitions in m.user_defs
-// named by m.invariants[q] - INV_USER) into P; false with a message naming
-// the invariant and the construct otherwise.
-bool compile_user_invariants(const tlcg_model& m, const HostModel& hm, const std::vector<std::string>& names,
-                             UserProg* P, std::string* err) {
+// the constants' tables of a fresh program
+bool prog_tables(const HostModel& hm, UserProg* P, std::string* err) {
   std::memset(P, 0, sizeof *P);
   P->nk = hm.L.nk;
   P->nv = hm.L.nv;
@@ -2045,6 +2053,17 @@ bool compile_user_invariants(const tlcg_model& m, const HostModel& hm, const std
   // the packed key / value index is the position in the sorted KeySet / ValueSet (host_model.h)
   for (int i = 0; i < hm.L.nk; ++i) P->keyval[i] = P->keysorted[i] = (int32_t)hm.keyset[(size_t)i];
   for (int i = 0; i < hm.L.nv; ++i) P->valval[i] = P->valsorted[i] = (int32_t)hm.valueset[(size_t)i];
+  return true;
+}
+
+}  // namespace
+
+// Compiles the user invariants of a model (the definitions in m.user_defs
+// named by m.invariants[q] - INV_USER) into P; false with a message naming
+// the invariant and the construct otherwise.
+bool compile_user_invariants(const tlcg_model& m, const HostModel& hm, const std::vector<std::string>& names,
+                             UserProg* P, std::string* err) {
+  if (!prog_tables(hm, P, err)) return false;
   Compiler c(hm, P);
   for (Def& d : split_defs(m.user_defs ? m.user_defs : "")) c.defs[d.name] = d;
   P->n_user = (int32_t)names.size();
@@ -2057,6 +2076,256 @@ bool compile_user_invariants(const tlcg_model& m, const HostModel& hm, const std
     }
   }
   return true;
+}
+
+// ---------------------------------------------------------------- temporal properties
+// A property is a definition whose body, outer parentheses stripped, is
+//   <>(Q) | <>Name                      TLCG_PROP_EVENTUALLY
+//   []<>(Q) | []<>Name                  TLCG_PROP_INFINITELY_OFTEN
+//   (P) ~> (Q) | [](P => <>(Q))         TLCG_PROP_LEADS_TO
+// with P and Q state predicates of the subset above.  The form is read off the
+// token sequence (nothing here evaluates a temporal operator); P and Q are then
+// compiled from the definition's own text, everything outside them blanked, so
+// that lines and columns (bulleted lists, messages) stay the module's.
+namespace {
+
+struct PropScan {
+  const std::vector<Tok>& t;  // without the END token's index in any range
+  std::vector<long> mate;     // matching bracket of an opener, -1
+
+  explicit PropScan(const std::vector<Tok>& toks) : t(toks), mate(toks.size(), -1) {
+    std::vector<size_t> open;
+    for (size_t i = 0; i < t.size(); ++i) {
+      if (t[i].k != Tok::OP) continue;
+      const std::string& s = t[i].s;
+      if (s == "(" || s == "[" || s == "{" || s == "<<") {
+        open.push_back(i);
+      } else if (s == ")" || s == "]" || s == "}" || s == ">>") {
+        if (open.empty()) continue;
+        mate[open.back()] = (long)i;
+        open.pop_back();
+      }
+    }
+  }
+  bool op(size_t i, const char* s) const { return i < t.size() && t[i].k == Tok::OP && t[i].s == s; }
+  bool pair(size_t i, const char* a, const char* b) const {
+    return op(i, a) && op(i + 1, b) && t[i + 1].off == t[i].end;
+  }
+  bool diamond(size_t i) const { return pair(i, "<", ">"); }
+  bool leadsto(size_t i) const { return pair(i, "~", ">"); }
+  // the temporal or action-level construct that starts at token i ("" if none)
+  std::string temporal(size_t i, bool in_case) const {
+    if (op(i, "[]") && !in_case) return "[]";
+    if (diamond(i)) return "<>";
+    if (leadsto(i)) return "~>";
+    if (op(i, "'")) return "a primed variable (')";
+    if (op(i, "\\cdot")) return "\\cdot";
+    if (pair(i, "-", "+") && op(i + 2, "->")) return "-+->";
+    if (t[i].k == Tok::ID) {
+      if (t[i].s == "ENABLED" || t[i].s == "UNCHANGED") return t[i].s;
+      if (t[i].s.compare(0, 3, "WF_") == 0 || t[i].s.compare(0, 3, "SF_") == 0)
+        return "a fairness operator (" + t[i].s.substr(0, 3) + ")";
+    }
+    return "";
+  }
+  // the first such construct of [lo, hi): its token, or hi
+  size_t first_temporal(size_t lo, size_t hi, std::string* what) const {
+    bool in_case = false;
+    for (size_t i = lo; i < hi; ++i) {
+      if (t[i].k == Tok::ID && t[i].s == "CASE") in_case = true;  // ([] separates a CASE's arms)
+      const std::string w = temporal(i, in_case);
+      if (!w.empty()) {
+        if (what) *what = w;
+        return i;
+      }
+    }
+    return hi;
+  }
+  void strip(size_t* lo, size_t* hi) const {
+    while (*hi > *lo + 1 && op(*lo, "(") && mate[*lo] == (long)*hi - 1) {
+      ++*lo;
+      --*hi;
+    }
+  }
+  // the tokens of [lo, hi) outside every bracket, each passed to f
+  template <class F>
+  void top_level(size_t lo, size_t hi, F f) const {
+    for (size_t i = lo; i < hi; ++i) {
+      f(i);
+      if (mate[i] >= 0 && (size_t)mate[i] < hi) i = (size_t)mate[i];
+    }
+  }
+  [[noreturn]] void refuse(size_t i, const std::string& what) const {
+    const Tok& at = t[std::min(i, t.size() - 1)];
+    throw CompileError(what + " at " + where(at.line, at.col));
+  }
+  // the operand of a <>: (..) or a name, running to hi
+  void operand(size_t a, size_t hi, size_t* qa, size_t* qb) const {
+    if (a >= hi) refuse(a, "<> without an operand");
+    const bool paren = op(a, "(") && mate[a] == (long)hi - 1;
+    const bool name = hi == a + 1 && t[a].k == Tok::ID;
+    if (!paren && !name) {
+      std::string w;
+      const size_t at = first_temporal(a, hi, &w);
+      if (at < hi)
+        refuse(at, "a formula that combines temporal formulas (" + w + " after a <>; conjunctions of temporal "
+                   "formulas are not implemented)");
+      refuse(a, "a <> whose operand is neither parenthesised nor a bare name running to the end of the formula");
+    }
+    *qa = a;
+    *qb = hi;
+  }
+};
+
+struct NotTemporal {};
+
+// the form of a property's tokens and the token ranges of P ([pa, pb), empty
+// for the forms without one) and Q
+int prop_form(const std::vector<Tok>& toks, size_t* pa, size_t* pb, size_t* qa, size_t* qb) {
+  const PropScan s(toks);
+  size_t lo = 0, hi = toks.size() - 1;  // (the last token is END)
+  s.strip(&lo, &hi);
+  std::string w;
+  if (s.first_temporal(lo, hi, &w) == hi) throw NotTemporal();
+  for (size_t i = lo; i < hi; ++i) {
+    const std::string c = s.temporal(i, true);
+    if (!c.empty() && c != "<>" && c != "~>") s.refuse(i, c + " in a property (only <>, []<> and ~> over state predicates are implemented)");
+  }
+  if (s.op(lo, "/\\") || s.op(lo, "\\/"))
+    s.refuse(s.first_temporal(lo, hi, &w), "a bulleted list containing a temporal operator (" + w + ")");
+  *pa = *pb = lo;
+  int form;
+  if (s.diamond(lo)) {
+    if (s.op(lo + 2, "[]")) s.refuse(lo, "<>[] (eventually always)");
+    s.operand(lo + 2, hi, qa, qb);
+    form = TLCG_PROP_EVENTUALLY;
+  } else if (s.op(lo, "[]") && s.diamond(lo + 1)) {
+    s.operand(lo + 3, hi, qa, qb);
+    form = TLCG_PROP_INFINITELY_OFTEN;
+  } else if (s.op(lo, "[]")) {
+    // [](P => <>Q)
+    if (!(s.op(lo + 1, "(") && s.mate[lo + 1] == (long)hi - 1))
+      s.refuse(lo, "[] applied to something other than <>Q or a parenthesised P => <>Q");
+    size_t a = lo + 1, b = hi;
+    s.strip(&a, &b);
+    size_t imp = b;
+    s.top_level(a, b, [&](size_t i) {
+      if (imp == b && s.op(i, "=>")) imp = i;
+    });
+    if (imp == b) s.refuse(lo, "[] applied to something other than <>Q or a parenthesised P => <>Q");
+    size_t ra = imp + 1, rb = b;
+    s.strip(&ra, &rb);
+    if (!s.diamond(ra)) s.refuse(std::min(ra, b - 1), "[](P => F) where F is not <>Q");
+    if (s.op(ra + 2, "[]")) s.refuse(ra, "<>[] (eventually always)");
+    s.operand(ra + 2, rb, qa, qb);
+    *pa = a;
+    *pb = imp;
+    form = TLCG_PROP_LEADS_TO;
+  } else {
+    std::vector<size_t> arrows;
+    size_t imp = hi;
+    s.top_level(lo, hi, [&](size_t i) {
+      if (s.leadsto(i)) arrows.push_back(i);
+      if (imp == hi && (s.op(i, "=>") || s.op(i, "<=>") || s.op(i, "\\equiv"))) imp = i;
+    });
+    if (arrows.empty()) {
+      const size_t at = s.first_temporal(lo, hi, &w);
+      s.refuse(at, "a formula that combines temporal formulas (" + w + " below another operator; only <>Q, []<>Q, "
+                   "P ~> Q and [](P => <>Q) are implemented)");
+    }
+    if (arrows.size() > 1) s.refuse(arrows[1], "a second ~> in one formula");
+    if (imp != hi) s.refuse(imp, "a top-level " + toks[imp].s + " beside ~> (parenthesise the operands of ~>)");
+    *pa = lo;
+    *pb = arrows[0];
+    *qa = arrows[0] + 2;
+    *qb = hi;
+    form = TLCG_PROP_LEADS_TO;
+  }
+  if (form == TLCG_PROP_LEADS_TO) {
+    if (*pa >= *pb) s.refuse(*pb, "an implication or ~> without a left operand");
+    if (*qa >= *qb) s.refuse(*qa, "~> without a right operand");
+    // an unparenthesised \E, IF, ... would take the ~> into its body
+    s.top_level(*pa, *pb, [&](size_t i) {
+      const Tok& k = toks[i];
+      const bool open_ended = (k.k == Tok::OP && (k.s == "\\E" || k.s == "\\A")) ||
+                              (k.k == Tok::ID && (k.s == "CHOOSE" || k.s == "IF" || k.s == "LET" || k.s == "CASE"));
+      if (open_ended) s.refuse(i, "an unparenthesised " + k.s + " left of the temporal operator (its body would hold it)");
+    });
+  }
+  for (int side = 0; side < 2; ++side) {
+    const size_t a = side ? *qa : *pa, b = side ? *qb : *pb;
+    const size_t at = s.first_temporal(a, b, &w);
+    if (at < b) s.refuse(at, "a temporal operator (" + w + ") inside an operand that must be a state predicate");
+  }
+  return form;
+}
+
+// d's text with everything outside tokens [a, b) blanked
+std::string blank_outside(const std::string& text, const std::vector<Tok>& toks, size_t a, size_t b) {
+  std::string out = text;
+  const size_t from = toks[a].off, to = toks[b - 1].end;
+  for (size_t i = 0; i < out.size(); ++i)
+    if ((i < from || i >= to) && out[i] != '\n') out[i] = ' ';
+  return out;
+}
+
+}  // namespace
+
+int compile_property(const tlcg_model& m, const HostModel& hm, const std::string& name, int* form, UserProg* P,
+                     std::string* err) {
+  if (P && !prog_tables(hm, P, err)) return -1;
+  std::vector<Def> defs = split_defs(m.user_defs ? m.user_defs : "");
+  Def* d = nullptr;
+  for (Def& x : defs)
+    if (x.name == name) d = &x;  // (the last one, as the compiler's map keeps)
+  if (!d) {
+    *err = "property " + name + " is not defined";
+    return -3;
+  }
+  try {
+    if (!d->params.empty()) throw CompileError("it takes arguments");
+    const std::vector<Tok> toks = lex(d->text, d->line0);
+    if (toks.size() < 2) throw CompileError("its definition is empty");
+    size_t pa = 0, pb = 0, qa = 0, qb = 0;
+    const int f = prop_form(toks, &pa, &pb, &qa, &qb);
+    if (form) *form = f;
+    std::unique_ptr<UserProg> scratch;
+    if (!P) {  // the form alone still says whether P and Q compile
+      scratch.reset(new UserProg);
+      P = scratch.get();
+      if (!prog_tables(hm, P, err)) return -1;
+    }
+    Compiler c(hm, P);
+    for (Def& x : defs) c.defs[x.name] = x;
+    P->n_user = 2;
+    Def part;
+    part.name = name;
+    part.line0 = d->line0;
+    if (pa < pb) {
+      part.text = blank_outside(d->text, toks, pa, pb);
+      c.compile_def(0, part, "the left operand of property " + name,
+                    " at " + where(toks[pa].line, toks[pa].col));
+    } else {
+      c.compile_true(0);
+    }
+    Def q = part;
+    q.body = nullptr;
+    q.parsed = false;
+    q.text = blank_outside(d->text, toks, qa, qb);
+    c.compile_def(1, q, f == TLCG_PROP_LEADS_TO ? "the right operand of property " + name
+                                                 : "the operand of property " + name,
+                  " at " + where(toks[qa].line, toks[qa].col));
+  } catch (const NotTemporal&) {
+    *err = "property " + name + " is a state predicate, not a temporal formula";
+    return -2;
+  } catch (const CompileError& e) {
+    *err = "property " + name + " cannot be checked: " + e.what();
+    return -1;
+  } catch (const std::exception& e) {  // (a numeral past 64 bits: std::stoll)
+    *err = "property " + name + " cannot be checked: " + e.what();
+    return -1;
+  }
+  return 0;
 }
 
 // ---------------------------------------------------------------- device code

@@ -578,10 +578,6 @@ bool bind_model(const Config& cfg, const Module& mod, bool deadlock_flag, tlcg_m
       *err = "Error: The property " + name + " specified in the configuration file is not defined in the specification.";
       return false;
     }
-    if (name != "Termination" || !invariant_matches(mod, name)) {
-      *err = "Error: temporal property " + name + " is not one this checker implements (Termination as published).";
-      return false;
-    }
   }
   m->msg_sent_limit = (int32_t)msl;
   m->compaction_times_limit = (int32_t)ctl;
@@ -603,6 +599,14 @@ bool bind_model(const Config& cfg, const Module& mod, bool deadlock_flag, tlcg_m
     *err = "Error: too many invariants";
     return false;
   }
+  static std::string defs;  // (tlcg_model.user_defs points here)
+  static std::map<std::string, int> index;
+  auto ensure_defs = [&]() {
+    if (m->user_defs) return;
+    index.clear();
+    defs = user_defs_text(mod, &index);
+    m->user_defs = defs.c_str();
+  };
   m->n_invariants = 0;
   for (auto& name : cfg.invariants) {
     int id = -1;
@@ -615,13 +619,7 @@ bool bind_model(const Config& cfg, const Module& mod, bool deadlock_flag, tlcg_m
     if (id < 0 || !invariant_matches(mod, name)) {
       // an invariant the user added (or edited): compiled from its text by
       // libtlcgpu (user_inv.cpp), which refuses what it cannot check exactly
-      static std::string defs;  // (tlcg_model.user_defs points here)
-      static std::map<std::string, int> index;
-      if (!m->user_defs) {
-        index.clear();
-        defs = user_defs_text(mod, &index);
-        m->user_defs = defs.c_str();
-      }
+      ensure_defs();
       // a definition without body text (the built-in module's own Init, Next,
       // ...) is not in the index: refuse it rather than bind another one
       const auto it = index.find(name);
@@ -634,8 +632,34 @@ bool bind_model(const Config& cfg, const Module& mod, bool deadlock_flag, tlcg_m
     }
     m->invariants[m->n_invariants++] = id;
   }
+  // a PROPERTY other than Termination as published: a definition the temporal
+  // front end of libtlcgpu (user_inv.cpp) takes -- <>Q, []<>Q, P ~> Q over
+  // state predicates -- which refuses every other formula by name, line and
+  // construct; nothing is checked approximately
+  for (auto& name : cfg.properties) {
+    if (property_is_published_termination(mod, name)) continue;
+    ensure_defs();
+    int32_t form = 0;
+    char e[1024] = {0};
+    // (a model that does not build is reported by tlcg_check_model, with its own message)
+    const int rc = tlcg_check_model(m, nullptr, 0) == 0 ? tlcg_host_property_form(m, name.c_str(), &form, e, sizeof e) : 0;
+    if (rc == -1) {
+      *err = std::string("Error: ") + e;
+      *exit_code = 150;  // as a user invariant outside the subset
+      return false;
+    }
+    if (rc != 0) {  // a state predicate, or a definition whose text is not at hand
+      *err = "Error: temporal property " + name + " is not one this checker implements (a definition of the form "
+             "<>Q, []<>Q or P ~> Q over state predicates, or Termination as published).";
+      return false;
+    }
+  }
   *exit_code = 0;
   return true;
+}
+
+bool property_is_published_termination(const Module& mod, const std::string& name) {
+  return name == "Termination" && invariant_matches(mod, name);
 }
 
 }  // namespace tlchost

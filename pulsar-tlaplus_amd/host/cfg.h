@@ -80,4 +80,10 @@ std::string user_defs_text(const Module& m, std::map<std::string, int>* index);
 bool bind_model(const Config& cfg, const Module& mod, bool deadlock_flag, tlcg_model* m, std::string* err,
                 int* exit_code, int* fairness = nullptr);
 
+// A PROPERTY of the cfg is either Termination as published (checked by
+// tlcg_check_termination) or a definition of the form <>Q, []<>Q, P ~> Q the
+// temporal front end accepts (tlcg_check_property; bind_model has refused
+// every other one): which of the two `name` is.
+bool property_is_published_termination(const Module& mod, const std::string& name);
+
 }  // namespace tlchost

@@ -317,33 +317,66 @@ int main(int argc, char** argv) {
   // (tlcg_check_termination: the not-P part of the state graph, its stuck
   // states and, under fairness, its cycles)
   bool live_fail = false;
+  std::string violated;  // the property the counterexample above is of
   if (st.status == TLCG_DONE && !cfg.properties.empty()) {
     std::printf("Checking temporal properties for the complete state space with %llu total distinct states at (%s)\n",
                 (unsigned long long)st.distinct, now_str().c_str());
     const int words = tlcg_state_words(&model);
     std::vector<uint64_t> lstates((size_t)words << 16);
     std::vector<int32_t> lacts(1 << 16);
-    int32_t ln = 0;
-    tlcg_liveness lv;
     tlcg_opts lo = opts;
     lo.state_capacity = st.distinct;  // G' is a subset of the reachable states
     lo.log2_fpset_slots = 0;
-    char lerr[512] = {0};
     // (the check allocates its own device buffers beside the safety run's,
     // which the outdegree statistics below still read: per state of capacity
     // the store, parent, slot index and stuck flag, 21-29 B, and 2 FPSet slots
-    // of 20-28 B each -- 60-85 B; it halves the capacity until they fit and
-    // grows it x4 only if G' needs more, liveness.hip)
-    if (tlcg_check_termination(&model, &lo, fairness, &lv, lstates.data(), lacts.data(), (int32_t)lacts.size(), &ln,
-                               lerr, (int32_t)sizeof lerr) != 0) {
-      std::printf("Error: the liveness check failed: %s\n", lerr);
-      std::printf("Finished in %s at (%s)\n", duration_str(0).c_str(), now_str().c_str());
-      return 255;
-    }
-    std::printf("Finished checking temporal properties in %s at %s\n", duration_str(lv.wall_ms / 1000.0).c_str(),
-                now_str().c_str());
-    if (!lv.holds) {
+    // of 20-28 B each -- 60-85 B, and 21 B more for a property the user
+    // defined; it halves the capacity until they fit and grows it x4 only if
+    // the graph needs more, liveness.hip)
+    double live_ms = 0;
+    // the cfg's properties in order, up to the first one violated: Termination
+    // as published by tlcg_check_termination, a property the user defined
+    // (<>Q, []<>Q, P ~> Q) by tlcg_check_property
+    for (const std::string& pname : cfg.properties) {
+      int32_t ln = 0;
+      tlcg_liveness lv;
+      char lerr[1024] = {0};
+      int lrc;
+      if (property_is_published_termination(mod, pname)) {
+        lrc = tlcg_check_termination(&model, &lo, fairness, &lv, lstates.data(), lacts.data(), (int32_t)lacts.size(),
+                                     &ln, lerr, (int32_t)sizeof lerr);
+      } else {
+        tlcg_property pr;
+        lrc = tlcg_check_property(&model, &lo, fairness, pname.c_str(), &pr, lstates.data(), lacts.data(),
+                                  (int32_t)lacts.size(), &ln, lerr, (int32_t)sizeof lerr);
+        lv = pr.lv;
+        if (lrc == -7) {
+          // P or Q does not evaluate on a reachable state: an error, not a verdict
+          std::vector<char> buf(1 << 16);
+          std::printf("Error: Evaluating property %s failed: %s.\n", pname.c_str(), lerr);
+          std::printf("Error: The behavior up to this point is:\n");
+          for (int i = 0; i < ln; ++i) {
+            if (lacts[(size_t)i] < 0) std::printf("State %d: <Initial predicate>\n", i + 1);
+            else std::printf("State %d: <%s>\n", i + 1, action_location(mod, lacts[(size_t)i]).c_str());
+            tlcg_decode_words(&model, &lstates[(size_t)i * words], buf.data(), (int32_t)buf.size());
+            std::printf("%s\n\n", buf.data());
+          }
+          std::printf("Finished in %s at (%s)\n", duration_str(0).c_str(), now_str().c_str());
+          tlcg_destroy(ctx);
+          return 75;
+        }
+      }
+      if (lrc != 0) {
+        std::printf("Error: the liveness check failed: %s\n", lerr);
+        std::printf("Finished in %s at (%s)\n", duration_str(0).c_str(), now_str().c_str());
+        return 255;
+      }
+      live_ms += lv.wall_ms;
+      if (lv.holds) continue;
       live_fail = true;
+      violated = pname;
+      std::printf("Finished checking temporal properties in %s at %s\n", duration_str(live_ms / 1000.0).c_str(),
+                  now_str().c_str());
       std::vector<char> buf(1 << 16);
       std::printf("Error: Temporal properties were violated.\n\n");
       std::printf("Error: The following behavior constitutes a counter-example:\n\n");
@@ -356,7 +389,11 @@ int main(int argc, char** argv) {
       if (lv.loop_to < 0) std::printf("State %d: Stuttering\n", ln + 1);
       else std::printf("State %d: Back to state %d: <%s>\n", ln + 1, lv.loop_to + 1,
                        action_location(mod, lv.back_action).c_str());
+      break;
     }
+    if (!live_fail)
+      std::printf("Finished checking temporal properties in %s at %s\n", duration_str(live_ms / 1000.0).c_str(),
+                  now_str().c_str());
   }
   if (live_fail) {
     rc = 13;
@@ -501,9 +538,9 @@ int main(int argc, char** argv) {
   double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   std::printf("Finished in %s at (%s)\n", duration_str(secs).c_str(), now_str().c_str());
   if (o.json) {
-    std::printf("{\"status\": %d, \"generated\": %llu, \"distinct\": %llu, \"depth\": %d, \"kernel_ms\": %.3f, \"seconds\": %.4f}\n",
+    std::printf("{\"status\": %d, \"generated\": %llu, \"distinct\": %llu, \"depth\": %d, \"kernel_ms\": %.3f, \"seconds\": %.4f%s}\n",
                 st.status, (unsigned long long)st.generated, (unsigned long long)st.distinct, st.depth, st.kernel_ms,
-                secs);
+                secs, violated.empty() ? "" : (", \"violated_property\": \"" + violated + "\"").c_str());
   }
   tlcg_destroy(ctx);
   return rc;

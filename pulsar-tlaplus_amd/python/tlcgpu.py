@@ -67,7 +67,14 @@ class tlcg_liveness(C.Structure):
                 ("reserved", C.c_int32), ("kernel_ms", C.c_double), ("wall_ms", C.c_double)]
 
 
+class tlcg_property(C.Structure):
+    _fields_ = [("lv", tlcg_liveness), ("form", C.c_int32), ("seed_at", C.c_int32), ("reachable", C.c_uint64),
+                ("seeds", C.c_uint64), ("error_state", C.c_int64), ("classify_ms", C.c_double)]
+
+
 FAIRNESS = {"none": 0, "wf": 1}
+PROP_FORMS = {0: "eventually", 1: "infinitely_often", 2: "leads_to"}
+PROP_FORM_IDS = {v: k for k, v in PROP_FORMS.items()}
 LIVE_KINDS = {0: "holds", 1: "stuttering", 2: "cycle"}
 
 _lib = None
@@ -154,6 +161,15 @@ def load_library(path: str = LIB_PATH):
                                                    C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32, I32, O, I32,
                                                    C.POINTER(tlcg_liveness), C.POINTER(U64), C.POINTER(I32), I32,
                                                    C.POINTER(I32), C.c_char_p, I32]),
+        "tlcg_check_property": (C.c_int, [M, O, I32, C.c_char_p, C.POINTER(tlcg_property), C.POINTER(U64),
+                                          C.POINTER(I32), I32, C.POINTER(I32), C.c_char_p, I32]),
+        "tlcg_property_graph_selftest": (C.c_int, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                                   C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.c_uint32,
+                                                   C.c_uint32, I32, O, I32, I32, C.POINTER(tlcg_property),
+                                                   C.POINTER(U64), C.POINTER(I32), I32, C.POINTER(I32), C.c_char_p,
+                                                   I32]),
+        "tlcg_host_property_form": (C.c_int, [M, C.c_char_p, C.POINTER(I32), C.c_char_p, I32]),
+        "tlcg_host_property_eval": (C.c_int, [M, C.c_char_p, C.POINTER(U64), U64, C.POINTER(C.c_uint8)]),
         "tlcg_jit_selftest": (C.c_int, [M, C.c_char_p, I32, C.c_char_p, I32][:1] + [C.c_char_p, C.c_char_p, I32]),
     }
     for name, (res, args) in sig.items():
@@ -420,6 +436,115 @@ def liveness_graph(row: Sequence[int], col: Sequence[int], is_p: Sequence[int], 
     return Liveness(bool(out.holds), LIVE_KINDS[out.kind], fairness, out.depth, out.states_notp, out.init_notp,
                     out.edges_notp, out.stuck, out.on_cycles, out.peel_rounds, trace, out.loop_to,
                     out.back_action if out.loop_to >= 0 else None, out.kernel_ms, out.wall_ms)
+
+
+@dataclass
+class Property(Liveness):
+    """A user-defined <>Q, []<>Q or P ~> Q checked on the GPU (tlcg_check_property):
+    Liveness' fields describe G', the states the seeds reach through ~Q states."""
+    form: str = "eventually"     # "eventually", "infinitely_often" or "leads_to"
+    seed_at: int = -1            # index in the trace of the seed state
+    reachable: int = 0           # reachable states (phase 1)
+    seeds: int = 0
+    error_state: int = -1        # store index of the first P/Q evaluation error
+    error: Optional[str] = None  # its message; the trace is then the BFS path to that state
+    classify_ms: float = 0.0
+
+
+def _property_of(out, fairness, trace, back, error=None) -> Property:
+    lv = out.lv
+    return Property(bool(lv.holds) and error is None, "error" if error else LIVE_KINDS[lv.kind], fairness, lv.depth,
+                    lv.states_notp, lv.init_notp, lv.edges_notp, lv.stuck, lv.on_cycles, lv.peel_rounds, trace,
+                    lv.loop_to, back if lv.loop_to >= 0 else None, lv.kernel_ms, lv.wall_ms, PROP_FORMS[out.form],
+                    out.seed_at, out.reachable, out.seeds, out.error_state, error, out.classify_ms)
+
+
+def host_property_form(model: Model, name: str) -> str:
+    """The form of property `name` (a definition of model.user_defs): "eventually",
+    "infinitely_often" or "leads_to"; ValueError with the front end's message
+    when it is refused.  Host only."""
+    m = model.to_c()
+    form = C.c_int32(-1)
+    err = C.create_string_buffer(1024)
+    rc = load_library().tlcg_host_property_form(C.byref(m), name.encode(), C.byref(form), err, len(err))
+    if rc != 0:
+        raise ValueError(err.value.decode())
+    return PROP_FORMS[form.value]
+
+
+def host_property_eval(model: Model, name: str, states: Sequence[int]) -> List[int]:
+    """P and Q of property `name` on every state, by the host interpreter:
+    bit 0 P (set for the forms without one), bit 1 Q, bit 2 an evaluation error"""
+    m = model.to_c()
+    w = state_words(model)
+    buf = (C.c_uint64 * max(1, len(states) * w))()
+    for i, s in enumerate(states):
+        for k in range(w):
+            buf[i * w + k] = (s >> (64 * k)) & 0xFFFFFFFFFFFFFFFF
+    out = (C.c_uint8 * max(1, len(states)))()
+    rc = load_library().tlcg_host_property_eval(C.byref(m), name.encode(), buf, len(states), out)
+    if rc != 0:
+        raise ValueError(f"tlcg_host_property_eval: {rc}")
+    return list(out)[:len(states)]
+
+
+def check_property(model: Model, name: str, fairness: str = "none", device: int = 0, state_capacity: int = 0,
+                   log2_fpset_slots: int = 0) -> Property:
+    r"""TLC's liveness check of a property the user defines (model.user_defs:
+    <>Q, []<>Q, P ~> Q or [](P => <>Q)) under Spec ("none") or Spec /    WF_vars(Next) ("wf"), through tlcg_check_property.  A refused property is a
+    ValueError; an evaluation error of P or Q on a reachable state comes back
+    as kind "error" with error_state, the message and the path to that state."""
+    lib = load_library()
+    m = model.to_c()
+    o = tlcg_opts()
+    o.device, o.state_capacity, o.log2_fpset_slots = device, state_capacity, log2_fpset_slots
+    out = tlcg_property()
+    w = state_words(model)
+    cap = 1 << 12
+    states = (C.c_uint64 * (cap * w))()
+    acts = (C.c_int32 * cap)()
+    n = C.c_int32(0)
+    err = C.create_string_buffer(1024)
+    rc = lib.tlcg_check_property(C.byref(m), C.byref(o), FAIRNESS[fairness], name.encode(), C.byref(out), states,
+                                 acts, cap, C.byref(n), err, len(err))
+    if rc == -2:
+        raise ValueError(err.value.decode())
+    if rc != 0 and rc != -7:
+        raise RuntimeError(f"tlcg_check_property: {rc}: {err.value.decode()}")
+    trace = [("Init" if acts[i] < 0 else ACTIONS[acts[i]], _from_words(states, i, w)) for i in range(n.value)]
+    back = ACTIONS[out.lv.back_action] if out.lv.loop_to >= 0 else None
+    return _property_of(out, fairness, trace, back, err.value.decode() if rc == -7 else None)
+
+
+def property_graph(row: Sequence[int], col: Sequence[int], is_p: Sequence[int], is_q: Sequence[int], n_init: int,
+                   form: str, words: int = 1, fairness: str = "none", device: int = 0, state_capacity: int = 0,
+                   log2_fpset_slots: int = 0) -> Property:
+    """The property pass on an explicit CSR graph (tlcg_property_graph_selftest):
+    as liveness_graph, with is_p[n] / is_q[n] the classes of the nodes and form
+    one of PROP_FORMS' names.  The trace holds (edge ordinal or "Init", word)."""
+    lib = load_library()
+    n = len(is_q)
+    if len(row) != n + 1 or len(col) != row[n] or len(is_p) != n:
+        raise ValueError("row must hold n + 1 offsets, the last one len(col); is_p and is_q n bytes")
+    c_row = (C.c_uint32 * (n + 1))(*row)
+    c_col = (C.c_uint32 * max(1, len(col)))(*col)
+    c_p = (C.c_uint8 * max(1, n))(*is_p)
+    c_q = (C.c_uint8 * max(1, n))(*is_q)
+    o = tlcg_opts()
+    o.device, o.state_capacity, o.log2_fpset_slots = device, state_capacity, log2_fpset_slots
+    out = tlcg_property()
+    cap = 3 * n + 3
+    states = (C.c_uint64 * (cap * words))()
+    acts = (C.c_int32 * cap)()
+    ln = C.c_int32(0)
+    err = C.create_string_buffer(512)
+    rc = lib.tlcg_property_graph_selftest(c_row, c_col, c_p, c_q, n, n_init, words, C.byref(o), FAIRNESS[fairness],
+                                          PROP_FORM_IDS[form], C.byref(out), states, acts, cap, C.byref(ln), err,
+                                          len(err))
+    if rc != 0:
+        raise RuntimeError(f"tlcg_property_graph_selftest: {rc}: {err.value.decode()}")
+    trace = [("Init" if acts[i] < 0 else acts[i], _from_words(states, i, words)) for i in range(ln.value)]
+    return _property_of(out, fairness, trace, out.lv.back_action)
 
 
 @dataclass
