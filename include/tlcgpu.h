@@ -293,6 +293,15 @@ int tlcg_host_check_invariants_batch(const tlcg_model* m, const uint64_t* states
  * only.  Returns the states compared (0: the component engine does not take
  * this model), or < 0 on a disagreement. */
 int64_t tlcg_host_component_selfcheck(const tlcg_model* m, uint64_t first, uint64_t n);
+/* Self-check of the per-lane component kernel's table-borne predicates, host
+ * only: on every component code and every class of component constants
+ * (Len(messages) 0..N x the 32 combinations of the five invariant flags), the
+ * code's invariant features and-ed with the component's mask against the
+ * evaluated built-in invariants, and the step table's stutter flag against
+ * the evaluated stutter count.  Returns the (code, class) pairs checked, 0
+ * when the per-lane pass does not take this model, -(1 + index) of the first
+ * pair that disagrees, -1 on a bad model. */
+int64_t tlcg_host_lane_inv_selfcheck(const tlcg_model* m);
 /* The component tree's closed-mode FPSet on the component of initial state
  * `comp`, replayed on the host with the engine's slot hash (the tuned
  * multiplier and the perfect-hash displacement table built from component

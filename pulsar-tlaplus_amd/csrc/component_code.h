@@ -408,9 +408,15 @@ TLCG_HD int compactor_step_cb(const Layout& L, const CodeConsts& K, ckey c, ckey
 // set, the bits cleared, the copied fields' mask and the result (0 disabled,
 // 1 enabled, 2 evaluation error), and a lane forms its state's successor as
 // (c & ~clear) | set | (copied & mask).  Index ph | r << 3 | m << 4: 64
-// entries for C <= 3 (the 16-bit codes of the per-lane kernel).  Checked
-// against compactor_step_cb on every code (tlcg_host_component_selfcheck).
+// entries for C <= 3 (the 16-bit codes of the per-lane kernel).  Bit 50 of an
+// entry (STEP_TERM) says that Terminating's stutter (:205-214) reads as
+// enabled from the code -- phase WRITE with every ledger written, m = C --
+// which the same three index fields decide (selfloop_count_c's code half; the
+// component's half is Len = N and term_ok).  Checked against
+// compactor_step_cb and selfloop_count_c on every code
+// (tlcg_host_component_selfcheck, tlcg_host_lane_inv_selfcheck).
 constexpr int STEP_TAB = 64;
+constexpr int STEP_TERM = 50;
 TLCG_HD u64 compactor_step_entry(const Layout& L, int idx) {
   const int ph = idx & 7, r = (idx >> 3) & 1, m = idx >> 4;
   const uint32_t xm = lmask(L.ctx_w) << cc_x(L), ccm = lmask(L.curc_w) << cc_cc(L);
@@ -439,18 +445,28 @@ TLCG_HD u64 compactor_step_entry(const Layout& L, int idx) {
     res = m == 0 ? 2 : 1;
   }
   set |= (ph >= PH_DELETE ? (uint32_t)PH_ONE : (uint32_t)ph + 1) << cc_ph(L);
-  return (u64)set | ((u64)clr << 16) | ((u64)cpy << 32) | ((u64)res << 48);
+  const u64 term = ph == PH_WRITE && m == L.C ? 1 : 0;
+  return (u64)set | ((u64)clr << 16) | ((u64)cpy << 32) | ((u64)res << 48) | (term << STEP_TERM);
 }
-// compactor_step_cb through the entries (tab: STEP_TAB of them)
-TLCG_HD int compactor_step_tab(const Layout& L, const CodeConsts& K, const u64* tab, ckey c, ckey* t, int* act) {
+// compactor_step_cb through the entries (tab: STEP_TAB of them); *term (when
+// asked for): the entry's STEP_TERM flag
+TLCG_HD int compactor_step_tab(const Layout& L, const CodeConsts& K, const u64* tab, ckey c, ckey* t, int* act,
+                               uint32_t* term = nullptr) {
   const uint32_t ph = cget(c, cc_ph(L), 3), r = (c >> cc_r(L)) & 1;
   const u64 e = tab[ph | (r << 3) | ((uint32_t)c_max_ledger(L, c) << 4)];
   const uint32_t set = (uint32_t)e & 0xFFFFu, clr = (uint32_t)(e >> 16) & 0xFFFFu, cpy = (uint32_t)(e >> 32) & 0xFFFFu;
   const uint32_t copied = (((c >> cc_h(L)) & 1u) << cc_ch(L)) | (cget(c, cc_x(L), L.ctx_w) << cc_cc(L));
   *t = (c & ~clr) | set | (copied & cpy);
-  const int res = ph == PH_ONE && K.len == 0 ? 0 : (int)(e >> 48);
+  const int res = ph == PH_ONE && K.len == 0 ? 0 : (int)(e >> 48) & 3;
+  if (term) *term = (uint32_t)(e >> STEP_TERM) & 1u;
   if (res) *act = ACT_PHASEONE + (int)ph;
   return res;
+}
+// selfloop_count_c from the entry's flag: Consumer when modelled, and
+// Terminating when the code's half (term) and the component's both hold
+TLCG_HD int lane_term_consts(const Layout& L, const CodeConsts& K) { return (int)K.len == L.N && L.term_ok ? 1 : 0; }
+TLCG_HD int selfloop_count_tab(const Layout& L, int term_consts, uint32_t term) {
+  return (L.consumer ? 1 : 0) + (int)(term & (uint32_t)term_consts);
 }
 
 // BrokerCrash, compaction.tla:169-182.  Returns 1 if enabled.
@@ -591,6 +607,71 @@ TLCG_HD int check_invariants_cbt(const Layout& L, const CodeConsts& K, ckey c) {
 #else
   return check_invariants_cb<W>(L, K, c);
 #endif
+}
+
+// check_invariants_cb's "does any invariant fail" split into a half that
+// reads only the code and a half that reads only the component (round 7, the
+// per-lane kernel component_lane.h): lane_inv_feat(L, c) has one bit per
+// code-only condition below, lane_inv_mask(L, K) the bits whose condition of
+// the component (and of the cfg: an invariant it does not name has none)
+// makes that feature a failure, and
+//   (lane_inv_feat(L, c) & lane_inv_mask(L, K)) != 0
+// exactly when check_invariants_cb(L, K, c) != -1, for every code c <
+// 2^code_bits and every K with len <= N (tlcg_host_lane_inv_selfcheck checks
+// it on every code and every class of K).  The host writes the features into
+// the top half of the per-lane kernel's owner table, which every probe reads
+// anyway; which invariant failed, and how, check_invariants_direct says.
+//
+//   feature of the code                           fails when (component, cfg)
+//   LF_ANY    always                              !msgs_ok (or len > N), TypeSafe;
+//                                                 an invariant that is none of the four
+//   LF_TYPE   a TypeSafe conjunct of the code     TypeSafe
+//             alone fails (phase, context, crash
+//             times; cursor with horizon 0 or a
+//             context outside 1..C)
+//   LF_CURH   cursor present, its horizon = Len   len = 0, TypeSafe
+//   LF_HZ_ERR horizon = Len, context ledger not   len > 0, hz_live, Horizon
+//             ok (evaluating it fails)
+//   LF_HZ_OK  horizon = Len, context ledger ok    len > 0, hz_live, hz_false, Horizon
+//   LF_DN_ERR context != 0, its ledger not ok     RetainNullKey, DuplicateNullKeyMessage
+//   LF_DN_H0  context != 0, ledger ok, horizon 0  ... and dn0
+//   LF_DN_H1  context != 0, ledger ok, horizon =  ... and dn1
+//             Len
+//   LF_LEAK   more than 2 ledgers present         CompactedLedgerLeak
+enum LaneFeat : uint32_t {
+  LF_ANY = 1, LF_TYPE = 2, LF_CURH = 4, LF_HZ_ERR = 8, LF_HZ_OK = 16, LF_DN_ERR = 32, LF_DN_H0 = 64, LF_DN_H1 = 128,
+  LF_LEAK = 256
+};
+TLCG_HD uint32_t lane_inv_feat(const Layout& L, ckey c) {
+  const uint32_t hb = (c >> cc_h(L)) & 1, cp = (c >> cc_cp(L)) & 1, ch = (c >> cc_ch(L)) & 1;
+  const uint32_t X = cget(c, cc_x(L), L.ctx_w);
+  const int cc = (int)cget(c, cc_cc(L), L.curc_w);
+  const bool ctx_ok = ctx_ledger_ok(L, c);
+  const bool type_bad = c_phase(L, c) > PH_DELETE || (int)X > L.C || (int)cget(c, cc_cr(L), L.cr_w) > L.K ||
+                        (cp && (!ch || cc < 1 || cc > L.C));
+  uint32_t f = LF_ANY;
+  if (type_bad) f |= LF_TYPE;
+  if (cp && ch) f |= LF_CURH;
+  if (hb) f |= ctx_ok ? LF_HZ_OK : LF_HZ_ERR;
+  if (X != 0) f |= !ctx_ok ? LF_DN_ERR : hb ? LF_DN_H1 : LF_DN_H0;
+  if (inv_leak_c(L, c) != EV_TRUE) f |= LF_LEAK;
+  return f;
+}
+TLCG_HD uint32_t lane_inv_mask(const Layout& L, const CodeConsts& K) {
+  uint32_t m = 0;
+  for (int q = 0; q < L.n_inv; ++q) {
+    if (L.inv[q] == INV_TYPESAFE)
+      m |= ((!K.msgs_ok || (int)K.len > L.N) ? LF_ANY : 0u) | LF_TYPE | (K.len == 0 ? LF_CURH : 0u);
+    else if (L.inv[q] == INV_LEAK)
+      m |= LF_LEAK;
+    else if (L.inv[q] == INV_HORIZON)
+      m |= (K.len > 0 && K.hz_live) ? LF_HZ_ERR | (K.hz_false ? LF_HZ_OK : 0u) : 0u;
+    else if (L.inv[q] == INV_DUPNULL)
+      m |= L.retain ? LF_DN_ERR | (K.dn0 ? LF_DN_H0 : 0u) | (K.dn1 ? LF_DN_H1 : 0u) : 0u;
+    else
+      m |= LF_ANY;  // (not a built-in: check_invariants_cb's answer is an error on every code)
+  }
+  return m;
 }
 
 // every invariant in cfg order, the user's by their programs (no tables)

@@ -22,6 +22,21 @@
 //     two independent LDS reads (the shared owner word, the lane's bit word)
 //     instead of a slot read and then its queue entry, and an insert is two
 //     LDS writes.
+//   - invariants (round 7): code + 1 takes the low 16 bits of an owner word,
+//     and the host writes the code's invariant features into the top 16
+//     (component_code.h lane_inv_feat: the half of "does a built-in invariant
+//     fail" that reads only the code).  The half that reads only the
+//     component is a mask in one register (lane_inv_mask, once per
+//     component), so an inserted successor's invariants are the probe's own
+//     owner word >> 16, and-ed with the mask: non-zero exactly when one fails
+//     (checked on every code and class of component,
+//     tlcg_host_lane_inv_selfcheck).  Such a state goes to the rare branch,
+//     where check_invariants_direct names the first failing invariant in cfg
+//     order and its kind.  Every state still has its own invariants decided:
+//     its own code's features against its own component's mask.
+//   - stutters (round 7): the code's half of "Terminating is enabled" is a
+//     flag of the compactor step's table entry (compactor_step_entry
+//     STEP_TERM), the component's half one register.
 //   - FIFO: the FPSet no longer points into the queue, so a lane keeps only
 //     its unexpanded states, in a ring of LANE_R codes (lane columns); queue
 //     positions are counters (the records' numbering is component_body.h's).
@@ -52,6 +67,18 @@ constexpr int LANE_R = TLCG_LANE_R;  // FIFO ring entries per lane (a power of 2
 #ifndef TLCG_LANE_STEP_TAB
 #define TLCG_LANE_STEP_TAB 1
 #endif
+// an inserted successor's built-in invariants from the feature word the owner
+// table carries beside its code (component_code.h lane_inv_feat) and the
+// component's mask; 0: check_invariants_cbt on each (A/B).  The user
+// invariants' outcome tables are not folded in: a module with them keeps
+// check_invariants_cbt.
+#ifndef TLCG_LANE_INV_FEAT
+#define TLCG_LANE_INV_FEAT 1
+#endif
+#if defined(TLCG_USER_INV) || defined(TLCG_LANE_INV_UNCOND)
+#undef TLCG_LANE_INV_FEAT
+#define TLCG_LANE_INV_FEAT 0
+#endif
 
 // the sum over the wave of x (every lane active), in a scalar
 __device__ __forceinline__ uint32_t lane_wave_sum(uint32_t x) {
@@ -66,6 +93,10 @@ __device__ __forceinline__ uint32_t lane_wave_sum(uint32_t x) {
 template <int K, bool OD = false>
 __device__ __forceinline__ void component_lane_body(const CompArgs& a, const Layout& L) {
   static_assert(K <= 64, "records and the 16-bit level sums take K <= 64");
+  // level_add's wave sum keeps distinct and generated in 16-bit halves: a
+  // lane expands at most K - 2 states (`full`), each generates at most 4
+  // (the compactor's, BrokerCrash's, two stutters), 64 lanes are summed
+  static_assert(64 * (K - 2) * 4 < 65536, "level_add's 16-bit halves");
   constexpr int T = LANE_T, NW = T / 32, R = LANE_R;
   constexpr int LV = TLCG_CODE_MAXLV < COMP_MAXLV ? TLCG_CODE_MAXLV : COMP_MAXLV;  // levels tracked
   __shared__ uint16_t ring[R][64];             // the lanes' FIFOs (unexpanded codes)
@@ -114,6 +145,12 @@ __device__ __forceinline__ void component_lane_body(const CompArgs& a, const Lay
 #ifdef TLCG_USER_INV
     code_consts_user(L, ccon);  // the user invariants' outcome tables of this component
 #endif
+#if TLCG_LANE_INV_FEAT
+    const uint32_t cmask = lane_inv_mask(L, ccon);  // the features that are failures in this component
+#endif
+#if TLCG_LANE_STEP_TAB
+    const int term_c = lane_term_consts(L, ccon);
+#endif
     // the records of this batch: [K][64] 32-bit words, position p of lane l at
     // (p x 64 + l) x 4; a store at an offset past the range is dropped
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
@@ -130,7 +167,7 @@ __device__ __forceinline__ void component_lane_body(const CompArgs& a, const Lay
     const lkey k0 = act ? (lkey)(s0 >> mb) : 0;
     const ckey c0 = code_encode(L, k0);
     const unsigned p0 = lane_slot(c0, mult);
-    if (act && (code_decode(L, ccon, c0) != k0 || owner[p0] != c0 + 1u)) {
+    if (act && (code_decode(L, ccon, c0) != k0 || (owner[p0] & 0xFFFFu) != c0 + 1u)) {
       // no code, or not the code graph the slots were built for: the cascade
       ovf = true;
       alive = false;
@@ -157,7 +194,8 @@ __device__ __forceinline__ void component_lane_body(const CompArgs& a, const Lay
       ckey t = 0, t2 = 0;
       int action = 0;
 #if TLCG_LANE_STEP_TAB
-      const int r = compactor_step_tab(L, ccon, steps, s, &t, &action);  // compaction.tla:221-226
+      uint32_t term = 0;
+      const int r = compactor_step_tab(L, ccon, steps, s, &t, &action, &term);  // compaction.tla:221-226
 #else
       const int r = compactor_step_cb(L, ccon, s, &t, &action);
 #endif
@@ -174,7 +212,8 @@ __device__ __forceinline__ void component_lane_body(const CompArgs& a, const Lay
 #endif
       const uint32_t b1 = 1u << (p1 & 31), b2 = 1u << (p2 & 31);
       const bool e1 = alive && r == 1, e2 = alive && crash;
-      const bool in1 = o1 == t + 1u, in2 = o2 == t2 + 1u;
+      // (the low half of an owner word: the code + 1; the top half its features)
+      const bool in1 = (o1 & 0xFFFFu) == t + 1u, in2 = (o2 & 0xFFFFu) == t2 + 1u;
       // a successor outside the code set: this component is not S's, the cascade
       const bool out = (e1 && !in1) || (e2 && !in2);
       const bool new1 = e1 && in1 && !(w1 & b1) && !out;
@@ -195,15 +234,25 @@ __device__ __forceinline__ void component_lane_body(const CompArgs& a, const Lay
 #endif
       const ckey first_new = new1 ? t : t2;
       tail += (new1 ? 1 : 0) + (new2 ? 1 : 0);
+#if TLCG_LANE_STEP_TAB
+      const int nsucc = (e1 ? 1 : 0) + (e2 ? 1 : 0) + (alive ? selfloop_count_tab(L, term_c, term) : 0);  // + stutters
+#else
       const int nsucc = (e1 ? 1 : 0) + (e2 ? 1 : 0) + (alive ? selfloop_count_c(L, ccon, s) : 0);  // + stutters
+#endif
       lvgen += (unsigned)nsucc;
       if constexpr (OD) ocnt += alive ? 1u << (10 * (tail - tail0)) : 0u;  // new states this expansion discovered
       // the inserted successors' invariants (first failing + 1; INV_UNKNOWN
-      // + 1: an outcome table left it to the programs, the rare branch)
+      // + 1: the rare branch settles it -- a failing feature, or an outcome
+      // table that left it to the programs)
 #if defined(TLCG_LANE_INV_UNCOND) && !defined(TLCG_NO_INV)  // (A/B: both evaluated, no branch)
       const int q1 = check_invariants_cbt(L, ccon, t) + 1, q2 = check_invariants_cbt(L, ccon, t2) + 1;
       int ev1 = new1 ? q1 : 0;
       int ev2 = new2 ? q2 : 0;
+#elif TLCG_LANE_INV_FEAT && !defined(TLCG_NO_INV)
+      // (a feature of the code that is a failure in this component: which
+      // invariant and how, the rare branch says)
+      int ev1 = (new1 && ((o1 >> 16) & cmask)) ? INV_UNKNOWN + 1 : 0;
+      int ev2 = (new2 && ((o2 >> 16) & cmask)) ? INV_UNKNOWN + 1 : 0;
 #elif !defined(TLCG_NO_INV)  // (TLCG_NO_INV: experiment only, measures what the invariants cost)
       int ev1 = new1 ? check_invariants_cbt(L, ccon, t) + 1 : 0;
       int ev2 = new2 ? check_invariants_cbt(L, ccon, t2) + 1 : 0;

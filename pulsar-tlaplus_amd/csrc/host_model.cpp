@@ -330,13 +330,31 @@ bool build_slot_owner(const HostModel& hm, int T, uint32_t mult, uint32_t dmult,
   return true;
 }
 
-bool build_lane_phash(const HostModel& hm, uint32_t* mult, uint32_t* owner) {
+bool build_lane_phash(const HostModel& hm, uint32_t* mult, uint32_t* owner, std::string* why) {
   std::fill(owner, owner + LANE_T, 0u);
   *mult = 0;
-  if (hm.L.producer || code_bits(hm.L) > 16) return false;
+  const Layout& L = hm.L;
+  if (L.producer || code_bits(L) > 16) return false;
   std::vector<std::vector<uint32_t>> calls;
   std::vector<uint32_t> codes;
   if (!comp0_calls(hm, 63, 1, &calls, &codes)) return false;  // (>= 63 states: past the pass's K = 64 - 2)
+  // an owner word is code + 1 in its low half and the code's invariant
+  // features in its top half (component_code.h lane_inv_feat), which the
+  // kernel ands with each component's mask: only if that is
+  // check_invariants_cb's answer on every code of S, under the constants of
+  // the first components (tlcg_host_lane_inv_selfcheck: every code and class)
+  for (uint32_t c : codes) {
+    if (c + 1u > 0xFFFFu || lane_inv_feat(L, c) > 0xFFFFu) return false;
+    for (u64 idx = 0; idx < 16 && idx < hm.n_init && !hm.user; ++idx) {
+      const CodeConsts kc = code_consts(L, comp_msgs_init(L, (u64)init_state<u128>(L, idx)));
+      if (((lane_inv_feat(L, c) & lane_inv_mask(L, kc)) != 0) != (check_invariants_cb(L, kc, c) != -1)) {
+        if (why)
+          *why = "the per-lane pass is not taken: the invariant features of code " + std::to_string(c) +
+                 " disagree with check_invariants_cb on component " + std::to_string(idx);
+        return false;
+      }
+    }
+  }
   std::vector<uint32_t> used(LANE_T, 0);
   uint64_t x = 0x2545F4914F6CDD1Dull;  // a fixed sequence: the choice is deterministic
   for (int i = 0; i < (1 << 20); ++i) {
@@ -352,7 +370,7 @@ bool build_lane_phash(const HostModel& hm, uint32_t* mult, uint32_t* owner) {
         ok = false;
         break;
       }
-      used[sl] = c + 1u;
+      used[sl] = (c + 1u) | (lane_inv_feat(L, c) << 16);
     }
     if (ok) {
       *mult = m;
@@ -852,6 +870,8 @@ int64_t tlcg_host_component_selfcheck(const tlcg_model* m, uint64_t first, uint6
       const CodeConsts kc = code_consts(L, cm);
       u64 tab[STEP_TAB];
       for (int i = 0; i < STEP_TAB; ++i) tab[i] = compactor_step_entry(L, i);
+      const uint32_t imask = lane_inv_mask(L, kc);
+      const int term_c = lane_term_consts(L, kc);
       for (ckey cd = 0; cd < (1u << code_bits(L)); ++cd) {
         ckey t1 = 0, t2 = 0, t3 = 0;
         int a1 = -1, a2 = -1, a3 = -1;
@@ -859,9 +879,13 @@ int64_t tlcg_host_component_selfcheck(const tlcg_model* m, uint64_t first, uint6
         const int r2 = compactor_step_cb(L, kc, cd, &t2, &a2);
         if (r1 != r2 || a1 != a2 || (r1 == 1 && t1 != t2) || check_invariants_c(L, kc, cd) != check_invariants_cb(L, kc, cd))
           return -(1 + checked);
-        if (L.C <= 3) {  // the per-lane kernel's table form (component_lane.h)
-          const int r3 = compactor_step_tab(L, kc, tab, cd, &t3, &a3);
+        // the per-lane kernel's invariant features against the component's mask
+        if (((lane_inv_feat(L, cd) & imask) != 0) != (check_invariants_cb(L, kc, cd) != -1)) return -(1 + checked);
+        if (L.C <= 3) {  // the per-lane kernel's table form (component_lane.h), its stutter flag included
+          uint32_t term = 0;
+          const int r3 = compactor_step_tab(L, kc, tab, cd, &t3, &a3, &term);
           if (r3 != r1 || a3 != a1 || (r1 == 1 && t3 != t1)) return -(1 + checked);
+          if (selfloop_count_tab(L, term_c, term) != selfloop_count_c(L, kc, cd)) return -(1 + checked);
         }
       }
     }
@@ -919,6 +943,49 @@ int64_t tlcg_host_component_selfcheck(const tlcg_model* m, uint64_t first, uint6
         if (seen.insert(succ[i]).second) todo.push_back(succ[i]);
     }
   }
+  return checked;
+}
+
+// The per-lane kernel's two table-borne predicates (component_lane.h) on
+// every code below 2^code_bits and every class of component constants -- len
+// 0..N x the 32 combinations of msgs_ok, hz_live, hz_false, dn0, dn1,
+// reachable or not: the invariant features against the mask
+// (component_code.h lane_inv_feat / lane_inv_mask vs check_invariants_cb) and
+// the step entry's stutter flag (vs selfloop_count_c).  Returns the (code,
+// class) pairs checked, -(1 + index) of the first pair that disagrees, 0 for
+// a model the pass does not take, -1 on a bad model.
+int64_t tlcg_host_lane_inv_selfcheck(const tlcg_model* m) {
+  HostModel hm;
+  std::string e;
+  if (!m || !build_model(*m, &hm, &e)) return -1;
+  const Layout& L = hm.L;
+  if (L.producer || hm.user || L.N > 8 || L.C > 3 || code_bits(L) > 16) return 0;
+  u64 tab[STEP_TAB];
+  for (int i = 0; i < STEP_TAB; ++i) tab[i] = compactor_step_entry(L, i);
+  int64_t checked = 0;
+  for (int len = 0; len <= L.N; ++len)
+    for (int f = 0; f < 32; ++f) {
+      CodeConsts kc{};
+      kc.len = (uint32_t)len;
+      kc.ledbits = 1u;
+      kc.msgs_ok = f & 1;
+      kc.hz_live = (f >> 1) & 1;
+      kc.hz_false = (f >> 2) & 1;
+      kc.dn0 = (f >> 3) & 1;
+      kc.dn1 = (f >> 4) & 1;
+      const uint32_t imask = lane_inv_mask(L, kc);
+      const int term_c = lane_term_consts(L, kc);
+      for (ckey cd = 0; cd < (1u << code_bits(L)); ++cd) {
+        ckey t = 0;
+        int act = -1;
+        uint32_t term = 0;
+        compactor_step_tab(L, kc, tab, cd, &t, &act, &term);
+        if (((lane_inv_feat(L, cd) & imask) != 0) != (check_invariants_cb(L, kc, cd) != -1) ||
+            selfloop_count_tab(L, term_c, term) != selfloop_count_c(L, kc, cd))
+          return -(1 + checked);
+        ++checked;
+      }
+    }
   return checked;
 }
 

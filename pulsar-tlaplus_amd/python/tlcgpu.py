@@ -113,6 +113,7 @@ def load_library(path: str = LIB_PATH):
         "tlcg_host_successors": (C.c_int, [M, U64, C.POINTER(U64), C.POINTER(I32), I32]),
         "tlcg_host_check_invariants": (C.c_int, [M, U64]),
         "tlcg_host_component_selfcheck": (C.c_int64, [M, U64, U64]),
+        "tlcg_host_lane_inv_selfcheck": (C.c_int64, [M]),
         "tlcg_host_tree_slot_probes": (C.c_int, [M, U64, C.POINTER(C.c_int64)]),
         "tlcg_host_termination_counterexample": (C.c_int64, [M]),
         "tlcg_owner": (C.c_int, [P, U64]),
@@ -329,6 +330,15 @@ def host_component_selfcheck(model: Model, first: int, n: int) -> int:
     compared with the generic ones (< 0: a disagreement)."""
     m = model.to_c()
     return load_library().tlcg_host_component_selfcheck(C.byref(m), C.c_uint64(first), C.c_uint64(n))
+
+
+def host_lane_inv_selfcheck(model: Model) -> int:
+    """(code, class of component constants) pairs on which the per-lane
+    kernel's invariant features and stutter flag were compared with the
+    evaluated invariants and stutter count (0: the per-lane pass does not take
+    the model; < 0: a disagreement)."""
+    m = model.to_c()
+    return load_library().tlcg_host_lane_inv_selfcheck(C.byref(m))
 
 
 def host_tree_slot_probes(model: Model, comp: int):
