@@ -574,6 +574,16 @@ int tlcg_recover(tlcg_ctx* c, const char* path, tlcg_stats* st);
  * for `arch` without a device (with user invariants: also the global engine's
  * user-check module); returns the code-object bytes or <0 (err). */
 int tlcg_jit_selftest(const tlcg_model* m, const char* arch, char* err, int32_t cap);
+/* Test hook: every user invariant of m on n given states (tlcg_state_words
+ * words each), on the device.  path 0: the interpreter (eval_user, UVWord);
+ * 1: the generated code over UVWord (what tlcg_user_check runs); 2: the
+ * generated code over UVCode; 3: code_consts_user + user_eval_c (the tables
+ * as TLCG_UTAB selects them).  out[i * n_user + k] = EV_*, or 0xFF for a
+ * state without a component code (paths 2, 3); n_user counts the distinct
+ * user invariants of m.invariants, k in their first-use order.  0, or < 0
+ * with a message. */
+int tlcg_user_eval_selftest(const tlcg_model* m, const tlcg_opts* o, const uint64_t* states, uint64_t n,
+                            int32_t path, uint8_t* out, char* err, int32_t cap);
 
 /* HIP stream (hipStream_t) the context launches on, for event timing. */
 void* tlcg_stream(tlcg_ctx* c);

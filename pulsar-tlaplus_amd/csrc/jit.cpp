@@ -44,7 +44,8 @@ std::string layout_literal(const Layout& L) {
 // check kernel alone (tlcg_user_check, the global engine's; compiles in a
 // fraction of the whole module's time); 2 (JIT_WAVE) the component code
 // pass's one-walk-per-wavefront kernels, a module of their own so that they
-// are scheduled with options of their own (jit_opts)
+// are scheduled with options of their own (jit_opts); 4 (JIT_EVAL) the
+// per-state evaluation test hook alone (kernels.h user_eval_body)
 std::string program_source(const Layout& L, const std::string& user, int part = JIT_MAIN) {
   const bool check_only = part == JIT_CHECK;
   std::string s = "typedef unsigned char uint8_t; typedef unsigned short uint16_t; typedef unsigned int uint32_t; typedef int int32_t;\n"
@@ -87,6 +88,11 @@ std::string program_source(const Layout& L, const std::string& user, int part = 
   if (check_only) {
     s += "extern \"C\" __global__ __launch_bounds__(256) void tlcg_user_check(tlcg::UserCheckArgs a) "
          "{ tlcg::user_check_body<" + w + ">(a, kL); }\n";
+    return s;
+  }
+  if (part == JIT_EVAL) {
+    s += "extern \"C\" __global__ __launch_bounds__(256) void tlcg_user_eval_states(tlcg::UserEvalArgs a) "
+         "{ tlcg::user_eval_body<" + w + ">(a, kL); }\n";
     return s;
   }
   if (part == JIT_WAVE || part == JIT_WAVE_BIG) {
@@ -188,8 +194,8 @@ bool jit_compile(const Layout& L, const std::string& arch, std::vector<char>* co
                  const std::string& user, int part) {
   const std::string src = program_source(L, user, part);
   const char* dump_env = std::getenv("TLCG_JIT_DUMP");  // diagnostics: the generated source and code object
-  const std::string dump =
-      dump_env ? std::string(dump_env) + (part == JIT_CHECK ? ".check" : part >= JIT_WAVE ? ".wave" : "") : "";
+  const char* const suffix = part == JIT_CHECK ? ".check" : part == JIT_EVAL ? ".eval" : part >= JIT_WAVE ? ".wave" : "";
+  const std::string dump = dump_env ? std::string(dump_env) + suffix : "";
   if (dump_env) {
     std::ofstream f(dump);
     f << src;
@@ -290,6 +296,27 @@ bool jit_launch_user_check(const JitUserCheck& k, const UserCheckArgs& a, hipStr
   const uint64_t blocks = (a.n + 255) / 256;
   if (blocks > 0x7fffffffull) return false;
   UserCheckArgs copy = a;
+  void* args[] = {&copy};
+  return hipModuleLaunchKernel(k.fn, (unsigned)blocks, 1, 1, 256, 1, 1, 0, stream, args, nullptr) == hipSuccess;
+}
+
+bool jit_build_user_eval(const Layout& L, int device, const std::string& user, JitUserCheck* out, std::string* err) {
+  double cs = 0;
+  bool cached = false;
+  if (!load_module(L, device, user, JIT_EVAL, &out->module, &cached, &cs, err)) return false;
+  out->compile_s = cs;
+  if (hipModuleGetFunction(&out->fn, out->module, "tlcg_user_eval_states") != hipSuccess) {
+    *err = "hipModuleGetFunction tlcg_user_eval_states";
+    return false;
+  }
+  return true;
+}
+
+bool jit_launch_user_eval(const JitUserCheck& k, const UserEvalArgs& a, hipStream_t stream) {
+  if (!a.n) return true;
+  const uint64_t blocks = (a.n + 255) / 256;
+  if (blocks > 0x7fffffffull) return false;
+  UserEvalArgs copy = a;
   void* args[] = {&copy};
   return hipModuleLaunchKernel(k.fn, (unsigned)blocks, 1, 1, 256, 1, 1, 0, stream, args, nullptr) == hipSuccess;
 }

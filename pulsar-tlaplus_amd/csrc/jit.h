@@ -17,7 +17,8 @@ namespace tlcg {
 // the parts of the specialized source (jit.cpp program_source): one module each
 // JIT_WAVE_BIG: the wave kernels for a model with many components
 // (jit_build: WAVE_M_BIG components per lane at a 6-waves-per-SIMD target)
-enum JitPart { JIT_MAIN = 0, JIT_CHECK = 1, JIT_WAVE = 2, JIT_WAVE_BIG = 3 };
+// JIT_EVAL: the per-state evaluation test hook alone (tlcg_user_eval_states, kernels.h user_eval_body)
+enum JitPart { JIT_MAIN = 0, JIT_CHECK = 1, JIT_WAVE = 2, JIT_WAVE_BIG = 3, JIT_EVAL = 4 };
 
 struct JitKernels {
   hipModule_t module = nullptr;
@@ -68,6 +69,9 @@ struct JitUserCheck {
 bool jit_build_user_check(const Layout& L, int device, const std::string& user, JitUserCheck* out, std::string* err);
 void jit_release_user_check(JitUserCheck* k);
 bool jit_launch_user_check(const JitUserCheck& k, const UserCheckArgs& a, hipStream_t stream);
+// the test hook's kernel (JIT_EVAL), in a module of its own: the modules a check loads hold no kernel of it
+bool jit_build_user_eval(const Layout& L, int device, const std::string& user, JitUserCheck* out, std::string* err);
+bool jit_launch_user_eval(const JitUserCheck& k, const UserEvalArgs& a, hipStream_t stream);
 
 // the specialized tree kernel for cap 384 / 640 (4 groups) or 1024 / 2048 (1 group); false when not built or on a
 // launch error

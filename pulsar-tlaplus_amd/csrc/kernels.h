@@ -217,4 +217,41 @@ __device__ __forceinline__ void user_check_body(const UserCheckArgs& a, const La
 }
 #endif
 
+// ---- test hook (tlcg_user_eval_selftest): every user invariant on each of n
+// given states, one thread per state, out[i * n_user + k] = EV_* of invariant
+// k on state i.  path 1: the generated code over the word (what
+// user_check_body runs); 2: over the state's component code (UVCode, the
+// on-chip engines' view); 3: the outcome tables (code_consts_user +
+// user_eval_c).  A state whose word does not come back from its code has no
+// component code: 0xFF on paths 2 and 3.  (Path 0, the interpreter, is the
+// precompiled k_user_eval, tlcgpu.hip.)
+struct UserEvalArgs {
+  const void* states;
+  u64 n;
+  int path;
+  int n_user;
+  uint8_t* out;
+};
+
+#ifdef TLCG_USER_INV
+template <typename W>
+__device__ __forceinline__ void user_eval_body(const UserEvalArgs& a, const Layout& L) {
+  const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.n) return;
+  const W s = ((const W*)a.states)[i];
+  uint8_t* const out = a.out + i * (u64)a.n_user;
+  if (a.path == 1) {
+    for (int k = 0; k < a.n_user; ++k) out[k] = (uint8_t)tlcg_user_eval(k, UVWord<W>{L, s});
+    return;
+  }
+  CodeConsts K = code_consts(L, comp_msgs_init(L, (u64)s));  // (`messages` sits in the low word)
+  const ckey c = code_encode_w<W>(L, s);
+  const bool coded = L.N <= 8 && code_bits(L) <= 31 && code_word<W>(L, K, (W)K.msgs, c) == s;
+  if (coded && a.path == 3) code_consts_user<W>(L, K);
+  for (int k = 0; k < a.n_user; ++k)
+    out[k] = !coded ? (uint8_t)0xFF
+                    : (uint8_t)(a.path == 2 ? tlcg_user_eval(k, UVCode<W>{L, K, c}) : user_eval_c<W>(L, K, k, c));
+}
+#endif
+
 }  // namespace tlcg

@@ -172,6 +172,7 @@ def load_library(path: str = LIB_PATH):
         "tlcg_host_property_form": (C.c_int, [M, C.c_char_p, C.POINTER(I32), C.c_char_p, I32]),
         "tlcg_host_property_eval": (C.c_int, [M, C.c_char_p, C.POINTER(U64), U64, C.POINTER(C.c_uint8)]),
         "tlcg_jit_selftest": (C.c_int, [M, C.c_char_p, I32, C.c_char_p, I32][:1] + [C.c_char_p, C.c_char_p, I32]),
+        "tlcg_user_eval_selftest": (C.c_int, [M, O, C.POINTER(U64), U64, I32, C.POINTER(C.c_uint8), C.c_char_p, I32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -365,6 +366,36 @@ def host_check_invariants_batch(model: Model, states: Sequence[int]) -> List[int
     if load_library().tlcg_host_check_invariants_batch(C.byref(m), buf, len(states), out) != 0:
         raise ValueError(check_model(model) or "bad model")
     return list(out)[:len(states)]
+
+
+USER_EVAL_PATHS = {"interpreter": 0, "word": 1, "code": 2, "tables": 3}
+
+
+def user_eval_states(model: Model, states: Sequence[int], path: str, device: int = 0) -> List[bytes]:
+    """Every user invariant of the model on each given state, on the device
+    (tlcg_user_eval_selftest): one bytes object per distinct user invariant
+    of model.invariants, in first-use order, holding the EV_* outcome per
+    state (0 TRUE, 1 FALSE, 2 error; 0xFF on the paths "code" and "tables"
+    for a state without a component code)."""
+    lib = load_library()
+    m = model.to_c()
+    o = tlcg_opts()
+    o.device = device
+    w = state_words(model)
+    users = model.user_names()
+    nu = len(dict.fromkeys(n for n in model.invariants if n in users))
+    n = len(states)
+    buf = (C.c_uint64 * max(1, n * w))()
+    for i, s in enumerate(states):
+        for k in range(w):
+            buf[i * w + k] = (s >> (64 * k)) & 0xFFFFFFFFFFFFFFFF
+    out = (C.c_uint8 * max(1, n * nu))()
+    err = C.create_string_buffer(4096)
+    rc = lib.tlcg_user_eval_selftest(C.byref(m), C.byref(o), buf, n, USER_EVAL_PATHS[path], out, err, len(err))
+    if rc != 0:
+        raise RuntimeError(f"tlcg_user_eval_selftest: {rc}: {err.value.decode()}")
+    raw = bytes(out)[:n * nu]
+    return [raw[k::nu] for k in range(nu)]
 
 
 def host_check_invariants(model: Model, state: int) -> int:

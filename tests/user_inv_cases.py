@@ -2,6 +2,7 @@
 definitions a user adds to compaction.tla, and a synchronized BFS that pairs
 every reachable packed state of the product with the Python oracle's value
 of the same state (both enumerate Init and Next in TLC's order)."""
+import itertools
 import os
 import re
 import sys
@@ -77,10 +78,11 @@ def oracle_model(m: T.Model, user_defs=None):
                            user_defs=user_defs if user_defs is not None else m.user_defs)
 
 
-def paired_states(m: T.Model, limit=None):
-    """(packed word, oracle state) for every reachable state, in BFS order"""
+def paired_states(m: T.Model, limit=None, n_inits=None):
+    """(packed word, oracle state) for every reachable state, in BFS order
+    (n_inits: only the states reachable from the first n_inits initial states)"""
     om = oracle_model(m)
-    inits = list(om.inits())
+    inits = list(itertools.islice(om.inits(), n_inits))
     words = [T.host_init_state(m, i) for i in range(len(inits))]
     seen = {}
     order = []
