@@ -302,6 +302,20 @@ int64_t tlcg_host_component_selfcheck(const tlcg_model* m, uint64_t first, uint6
  * when the per-lane pass does not take this model, -(1 + index) of the first
  * pair that disagrees, -1 on a bad model. */
 int64_t tlcg_host_lane_inv_selfcheck(const tlcg_model* m);
+/* Self-check of the per-lane kernel's owner table, host only: every code of
+ * component 0's code set S (walked here on its own) sits in its slot with
+ * code + 1 (bits 0..15), its invariant features (16..24) and its step-table
+ * index (25..30) -- the index the step table's lookup computes, selecting
+ * the entry that gives the evaluated compactor successor -- in the first
+ * word and its dense index in the second, the dense indices a bijection
+ * onto 0..|S| - 1; every other slot is empty.  *overflow (may be NULL): 1
+ * when a field of some code of S does not fit its bits.  Returns |S|, 0 when
+ * the per-lane pass refuses this model (as it must when *overflow),
+ * -(1 + position) of the first code that disagrees, -1 on a bad model. */
+int64_t tlcg_host_lane_owner_selfcheck(const tlcg_model* m, int* overflow);
+/* The first word of the owner entry of an arbitrary component code (0: a
+ * field does not fit), -1 on a bad model.  Host only. */
+int64_t tlcg_host_lane_owner_word(const tlcg_model* m, uint32_t code);
 /* The component tree's closed-mode FPSet on the component of initial state
  * `comp`, replayed on the host with the engine's slot hash (the tuned
  * multiplier and the perfect-hash displacement table built from component

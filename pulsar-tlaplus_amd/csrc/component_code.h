@@ -448,12 +448,16 @@ TLCG_HD u64 compactor_step_entry(const Layout& L, int idx) {
   const u64 term = ph == PH_WRITE && m == L.C ? 1 : 0;
   return (u64)set | ((u64)clr << 16) | ((u64)cpy << 32) | ((u64)res << 48) | (term << STEP_TERM);
 }
-// compactor_step_cb through the entries (tab: STEP_TAB of them); *term (when
-// asked for): the entry's STEP_TERM flag
-TLCG_HD int compactor_step_tab(const Layout& L, const CodeConsts& K, const u64* tab, ckey c, ckey* t, int* act,
+// a code's index into the entries: ph | r << 3 | m << 4 (6 bits for C <= 3).
+// A function of the code alone, so the per-lane kernel's owner table carries
+// it beside the code (lane_owner_word) and a dequeued state brings it along.
+TLCG_HD uint32_t compactor_step_index(const Layout& L, ckey c) {
+  return cget(c, cc_ph(L), 3) | (((c >> cc_r(L)) & 1) << 3) | ((uint32_t)c_max_ledger(L, c) << 4);
+}
+// compactor_step_cb through entry e = tab[idx] of code c (ph = idx & 7);
+// *term (when asked for): the entry's STEP_TERM flag
+TLCG_HD int compactor_step_ent(const Layout& L, const CodeConsts& K, u64 e, uint32_t ph, ckey c, ckey* t, int* act,
                                uint32_t* term = nullptr) {
-  const uint32_t ph = cget(c, cc_ph(L), 3), r = (c >> cc_r(L)) & 1;
-  const u64 e = tab[ph | (r << 3) | ((uint32_t)c_max_ledger(L, c) << 4)];
   const uint32_t set = (uint32_t)e & 0xFFFFu, clr = (uint32_t)(e >> 16) & 0xFFFFu, cpy = (uint32_t)(e >> 32) & 0xFFFFu;
   const uint32_t copied = (((c >> cc_h(L)) & 1u) << cc_ch(L)) | (cget(c, cc_x(L), L.ctx_w) << cc_cc(L));
   *t = (c & ~clr) | set | (copied & cpy);
@@ -461,6 +465,12 @@ TLCG_HD int compactor_step_tab(const Layout& L, const CodeConsts& K, const u64* 
   if (term) *term = (uint32_t)(e >> STEP_TERM) & 1u;
   if (res) *act = ACT_PHASEONE + (int)ph;
   return res;
+}
+// ... with the index computed from the code (tab: STEP_TAB entries)
+TLCG_HD int compactor_step_tab(const Layout& L, const CodeConsts& K, const u64* tab, ckey c, ckey* t, int* act,
+                               uint32_t* term = nullptr) {
+  const uint32_t idx = compactor_step_index(L, c);
+  return compactor_step_ent(L, K, tab[idx], idx & 7u, c, t, act, term);
 }
 // selfloop_count_c from the entry's flag: Consumer when modelled, and
 // Terminating when the code's half (term) and the component's both hold
@@ -672,6 +682,19 @@ TLCG_HD uint32_t lane_inv_mask(const Layout& L, const CodeConsts& K) {
       m |= LF_ANY;  // (not a built-in: check_invariants_cb's answer is an error on every code)
   }
   return m;
+}
+
+// An entry of the per-lane kernel's owner table (round 8), two 32-bit words:
+//   word 0: code + 1 (bits 0..15) | lane_inv_feat (16..24) | compactor_step_index (25..30)
+//   word 1: the code's dense index in S (its BFS position, 0..|S| - 1 <= 61):
+//           its bit in a lane's 64-bit FPSet register
+// lane_owner_word: word 0 of code c, 0 when a field does not fit (the host
+// then refuses the pass, build_lane_phash)
+constexpr int LANE_OWNER_FEAT_SH = 16, LANE_OWNER_STEP_SH = 25;
+TLCG_HD uint32_t lane_owner_word(const Layout& L, ckey c) {
+  const uint32_t f = lane_inv_feat(L, c), ix = compactor_step_index(L, c);
+  if (c + 1u > 0xFFFFu || f > 0x1FFu || ix >= (uint32_t)STEP_TAB) return 0u;
+  return (c + 1u) | (f << LANE_OWNER_FEAT_SH) | (ix << LANE_OWNER_STEP_SH);
 }
 
 // every invariant in cfg order, the user's by their programs (no tables)

@@ -43,13 +43,26 @@
 //   - control: the BFS loop runs while any lane of the wave is alive, with
 //     every lane in it (a finished lane's updates are masked by selects, its
 //     record stores go out of the buffer's range), so the per-level counts of
-//     the lanes that close a level at one level are one DPP sum and one LDS
-//     add instead of 64 same-address LDS adds (component_body.h's bank
-//     conflicts), and the loop pays no exec-mask bookkeeping per branch.
-// LDS per 64-lane workgroup: the ring R x 128 B (the host picks R per layout,
-// jit.cpp / host_model.cpp lane_ring_entries: 8 entries, 1 KB, on G9; a wider
-// frontier sends the component to the cascade), the bits 2 KB, owner 1 KB (vs
-// 13.3 KB for component_body.h), so registers, not LDS, set the occupancy.
+//     the lanes that close a level at one level were one DPP sum and one LDS
+//     add instead of 64 same-address LDS adds (round 8 went back to an add
+//     per lane, TLCG_LANE_LEVEL_LDS: the sum's own instructions cost more),
+//     and the loop pays no exec-mask bookkeeping per branch.
+//   - round 8: an owner entry is two words (component_code.h lane_owner_word:
+//     code + 1 | features << 16 | the code's step-table index << 25, and the
+//     code's dense index in S).  The ring queues the first word instead of
+//     the bare code, so a dequeued state brings its step index with it, and
+//     the lane's FPSet is one 64-bit register indexed by the dense index (S
+//     has at most 62 codes) instead of T bits in LDS: a probe is one 64-bit
+//     LDS read, an insert none.  FPSet.put stays exact: c is in the set iff
+//     the low half of owner[slot(c)] is c + 1 and the lane's bit of that
+//     entry's dense index is set.
+// LDS per 64-lane workgroup: the ring R x 256 B (the host picks R per layout,
+// jit.cpp / host_model.cpp lane_ring_entries: 8 entries, 2 KB, on G9; a wider
+// frontier sends the component to the cascade), owner 2 KB, the step table
+// 0.5 KB, the level sums 0.25 KB: 4864 B as before round 8 (then the ring 1
+// KB, the bits 2 KB, owner 1 KB), 32 workgroups of the CU's 160 KB (vs 13.3
+// KB for component_body.h), so registers, not LDS, set the occupancy.  (With
+// TLCG_LANE_FP_REG=0 and the 32-bit ring it is 5888 B: 27 workgroups.)
 #pragma once
 #if !defined(__HIPCC_RTC__)
 #include "component_body.h"
@@ -79,6 +92,27 @@ constexpr int LANE_R = TLCG_LANE_R;  // FIFO ring entries per lane (a power of 2
 #undef TLCG_LANE_INV_FEAT
 #define TLCG_LANE_INV_FEAT 0
 #endif
+// round 8, each on by default and 0 for A/B:
+// the ring queues a state's 32-bit owner word instead of its bare code, so a
+// dequeued state brings its step-table index with it (bits 25..30,
+// component_code.h lane_owner_word) and the ffbh / phase / r index chain goes
+#ifndef TLCG_LANE_OWNER_RING
+#define TLCG_LANE_OWNER_RING 1
+#endif
+#if !TLCG_LANE_STEP_TAB  // (the index is the step table's)
+#undef TLCG_LANE_OWNER_RING
+#define TLCG_LANE_OWNER_RING 0
+#endif
+// the lane's FPSet as one 64-bit register, indexed by the code's dense index
+// in S (the owner entry's second word) instead of T bits in LDS lane columns
+#ifndef TLCG_LANE_FP_REG
+#define TLCG_LANE_FP_REG 1
+#endif
+// a level's counts as one LDS add per adding lane: no ballots, DPP sum or
+// lane reads at a level end (0: round 6's wave sum and one add, A/B)
+#ifndef TLCG_LANE_LEVEL_LDS
+#define TLCG_LANE_LEVEL_LDS 1
+#endif
 
 // the sum over the wave of x (every lane active), in a scalar
 __device__ __forceinline__ uint32_t lane_wave_sum(uint32_t x) {
@@ -99,28 +133,51 @@ __device__ __forceinline__ void component_lane_body(const CompArgs& a, const Lay
   static_assert(64 * (K - 2) * 4 < 65536, "level_add's 16-bit halves");
   constexpr int T = LANE_T, NW = T / 32, R = LANE_R;
   constexpr int LV = TLCG_CODE_MAXLV < COMP_MAXLV ? TLCG_CODE_MAXLV : COMP_MAXLV;  // levels tracked
-  __shared__ uint16_t ring[R][64];             // the lanes' FIFOs (unexpanded codes)
+#if TLCG_LANE_OWNER_RING
+  typedef uint32_t ring_t;                     // (owner words)
+#else
+  typedef uint16_t ring_t;                     // (codes)
+#endif
+  __shared__ ring_t ring[R][64];               // the lanes' FIFOs (unexpanded states)
+#if TLCG_LANE_FP_REG
+  __shared__ u64 owner[T];                     // slot s: its owner word (0: none) | dense index << 32, shared
+#else
   __shared__ uint32_t bits[NW][64];            // the lanes' FPSets: bit s of lane l = bit s % 32 of bits[s / 32][l]
-  __shared__ uint32_t owner[T];                // the code in slot s + 1 (0: none), shared
-  __shared__ unsigned long long lvl_sh[LV];    // per level: distinct (low 32) + generated (high 32)
+  __shared__ uint32_t owner[T];                // slot s: its owner word (code + 1 in the low half; 0: none), shared
+#endif
+  // per level: distinct (low 32) + generated (high 32); OD: then the expansions
+  // that discovered 0, 1 and 2 new states (kept here, not in registers of the
+  // loop: the kernel stays within the 64 VGPRs of 8 waves per SIMD)
+  constexpr int LVS = LV + (OD ? 3 : 0);
+  static_assert(LVS <= 64 && (K - 2) * 4 + 1 < 256, "one lane per level sum; OD packs three counts above lgen's 8 bits");
+  __shared__ unsigned long long lvl_sh[LVS];
 #if TLCG_LANE_STEP_TAB
   __shared__ u64 steps[STEP_TAB];              // the compactor disjunct's update masks (compactor_step_entry)
 #endif
   const int lane = threadIdx.x;
   const int mb = L.msg_sh + L.N * L.mw;
   const uint32_t mult = a.lane_mult;
-  for (int i = lane; i < T; i += 64) owner[i] = a.lane_owner[i];
+#if TLCG_LANE_FP_REG
+  for (int i = lane; i < T; i += 64) owner[i] = (u64)a.lane_owner[2 * i] | ((u64)a.lane_owner[2 * i + 1] << 32);
+#else
+  for (int i = lane; i < T; i += 64) owner[i] = a.lane_owner[2 * i];
+#endif
 #if TLCG_LANE_STEP_TAB
   for (int i = lane; i < STEP_TAB; i += 64) steps[i] = compactor_step_entry(L, i);
 #endif
-  if (lane < LV) lvl_sh[lane] = 0;
+  if (lane < LVS) lvl_sh[lane] = 0;
   uint32_t gen = 0, dist = 0, nexp = 0;  // (nexp: states expanded by the components that finish here)
-  unsigned od0 = 0, od1 = 0, od2 = 0;
   unsigned long long ev = NO_EVENT;
   __syncthreads();
-  // a level's per-lane counts (x: distinct | generated << 16) into lvl_sh:
-  // one DPP sum when every lane that adds adds at one level, else per lane
+  // a level's per-lane counts (x: distinct | generated << 16) into lvl_sh: one
+  // LDS add per adding lane (round 8: at 20 level ends per 62 iterations the
+  // same-address adds cost less than the ballots, the DPP sum and the lane
+  // reads that saved them); TLCG_LANE_LEVEL_LDS=0: one DPP sum when every
+  // lane that adds adds at one level, else per lane
   auto level_add = [&](bool add, int lvc, uint32_t x) {
+#if TLCG_LANE_LEVEL_LDS
+    if (add) atomicAdd(&lvl_sh[lvc], (unsigned long long)(x & 0xFFFFu) | ((unsigned long long)(x >> 16) << 32));
+#else
     const unsigned long long m = __ballot(add);
     if (!m) return;
     const int l0 = __builtin_amdgcn_readlane(lvc, __ffsll((long long)m) - 1);
@@ -130,6 +187,7 @@ __device__ __forceinline__ void component_lane_body(const CompArgs& a, const Lay
     } else if (add) {
       atomicAdd(&lvl_sh[lvc], (unsigned long long)(x & 0xFFFFu) | ((unsigned long long)(x >> 16) << 32));
     }
+#endif
   };
   for (u64 b = blockIdx.x; b * 64 < a.n_comp; b += gridDim.x) {
     const u64 ci = b * 64 + (u64)lane;
@@ -138,8 +196,12 @@ __device__ __forceinline__ void component_lane_body(const CompArgs& a, const Lay
     const u64 entry = act ? (a.list ? a.list[ci] : a.comp0 + ci) : 0;
     const u64 idx0 = entry & ((1ull << 40) - 1);
     const int counted = (int)(entry >> 40);
+#if TLCG_LANE_FP_REG
+    u64 fp = 0;  // the lane's FPSet: bit d = the code of S with dense index d
+#else
 #pragma unroll
     for (int i = 0; i < NW; ++i) bits[i][lane] = 0u;  // (the lane's own columns)
+#endif
     const u64 s0 = init_state(L, idx0);
     CodeConsts ccon = code_consts(L, comp_msgs_init(L, s0));
 #ifdef TLCG_USER_INV
@@ -162,19 +224,28 @@ __device__ __forceinline__ void component_lane_body(const CompArgs& a, const Lay
     // the current level and stops at its end (end-of-level counts, as every
     // engine reports them); ovf: the component goes on to the cascade
     bool alive = act, ovf = false, stop = false;
-    uint32_t lgen = 0, lvgen = 0, ocnt = 0;
+    uint32_t lgen = 0, lvgen = 0;  // (OD: bits 8.., expansions by new states discovered)
     u64 lev = NO_EVENT;
     const lkey k0 = act ? (lkey)(s0 >> mb) : 0;
     const ckey c0 = code_encode(L, k0);
     const unsigned p0 = lane_slot(c0, mult);
-    if (act && (code_decode(L, ccon, c0) != k0 || (owner[p0] & 0xFFFFu) != c0 + 1u)) {
+    const uint32_t ow0 = (uint32_t)owner[p0];
+    if (act && (code_decode(L, ccon, c0) != k0 || (ow0 & 0xFFFFu) != c0 + 1u)) {
       // no code, or not the code graph the slots were built for: the cascade
       ovf = true;
       alive = false;
     }
     if (alive) {
+#if TLCG_LANE_FP_REG
+      fp = 1ull << (uint32_t)(owner[p0] >> 32);
+#else
       bits[p0 >> 5][lane] = 1u << (p0 & 31);
+#endif
+#if TLCG_LANE_OWNER_RING
+      ring[0][lane] = ow0;
+#else
       ring[0][lane] = (uint16_t)c0;
+#endif
       tail = 1;
       __builtin_amdgcn_raw_buffer_store_b32(comp_record(c0, 0, 0), rsrc, (int)loff, 0, 0);  // (position 0: the root)
       lgen = 1;
@@ -186,45 +257,78 @@ __device__ __forceinline__ void component_lane_body(const CompArgs& a, const Lay
       }
     }
     lvl_end = tail;
+#if TLCG_LANE_OWNER_RING
+    uint32_t cur = ow0;  // the state to expand: its owner word
+#else
     ckey cur = c0;
+#endif
     while (__ballot(alive)) {
-      const ckey s = cur;
       const int tail0 = tail;
-      const ckey nxt = ring[(head + 1) & (R - 1)][lane];
       ckey t = 0, t2 = 0;
       int action = 0;
+#if TLCG_LANE_OWNER_RING
+      // (a finished lane goes on with whatever its ring holds: the index is
+      // kept inside the table, every slot is below T)
+      const ckey s = (cur & 0xFFFFu) - 1u;
+      const uint32_t nxt = ring[(head + 1) & (R - 1)][lane];
+      const uint32_t six = (cur >> LANE_OWNER_STEP_SH) & (uint32_t)(STEP_TAB - 1);
+      uint32_t term = 0;
+      const int r = compactor_step_ent(L, ccon, steps[six], six & 7u, s, &t, &action, &term);  // compaction.tla:221-226
+#else
+      const ckey s = cur;
+      const ckey nxt = ring[(head + 1) & (R - 1)][lane];
 #if TLCG_LANE_STEP_TAB
       uint32_t term = 0;
       const int r = compactor_step_tab(L, ccon, steps, s, &t, &action, &term);  // compaction.tla:221-226
 #else
       const int r = compactor_step_cb(L, ccon, s, &t, &action);
 #endif
+#endif
       const bool crash = crash_step_c(L, s, &t2) != 0;            // :227
       // FPSet.put of both successors: slot, the shared owner, the lane's bits
       const unsigned p1 = lane_slot(t, mult), p2 = lane_slot(t2, mult);
+#if TLCG_LANE_FP_REG
+      const u64 oe1 = owner[p1], oe2 = owner[p2];
+      const uint32_t o1 = (uint32_t)oe1, o2 = (uint32_t)oe2;
+#else
       const uint32_t o1 = owner[p1], o2 = owner[p2];
       const uint32_t w1 = bits[p1 >> 5][lane];
       uint32_t w2 = bits[p2 >> 5][lane];
+#endif
 #ifndef TLCG_LANE_NO_SCHED_BARRIER
-      // (the four reads issued together, before anything that consumes them
-      // or writes LDS: one round trip per expansion, not two)
+      // (the reads issued together, before anything that consumes them or
+      // writes LDS: one round trip per expansion, not two)
       __builtin_amdgcn_sched_barrier(0);
 #endif
-      const uint32_t b1 = 1u << (p1 & 31), b2 = 1u << (p2 & 31);
       const bool e1 = alive && r == 1, e2 = alive && crash;
-      // (the low half of an owner word: the code + 1; the top half its features)
+      // (the low half of an owner word: the code + 1; above it its features)
       const bool in1 = (o1 & 0xFFFFu) == t + 1u, in2 = (o2 & 0xFFFFu) == t2 + 1u;
       // a successor outside the code set: this component is not S's, the cascade
       const bool out = (e1 && !in1) || (e2 && !in2);
+#if TLCG_LANE_FP_REG
+      // (a dense index is below 62: build_lane_phash)
+      const u64 b1 = 1ull << (uint32_t)(oe1 >> 32), b2 = 1ull << (uint32_t)(oe2 >> 32);
+      const bool new1 = e1 && in1 && !(fp & b1) && !out;
+      fp |= new1 ? b1 : 0ull;  // (the second sees the first's insert)
+      const bool new2 = e2 && in2 && !(fp & b2) && !out;
+      fp |= new2 ? b2 : 0ull;
+#else
+      const uint32_t b1 = 1u << (p1 & 31), b2 = 1u << (p2 & 31);
       const bool new1 = e1 && in1 && !(w1 & b1) && !out;
       if ((p2 >> 5) == (p1 >> 5) && new1) w2 |= b1;  // (the second sees the first's insert)
       const bool new2 = e2 && in2 && !(w2 & b2) && !out;
       bits[p1 >> 5][lane] = new1 ? w1 | b1 : w1;
       bits[p2 >> 5][lane] = new2 ? w2 | b2 : w2;
+#endif
       // the queue (the ring: a successor not inserted is overwritten or never
       // read) and each new state's record at its position
+#if TLCG_LANE_OWNER_RING
+      ring[tail & (R - 1)][lane] = o1;
+      ring[(tail + (new1 ? 1 : 0)) & (R - 1)][lane] = o2;
+#else
       ring[tail & (R - 1)][lane] = (uint16_t)t;
       ring[(tail + (new1 ? 1 : 0)) & (R - 1)][lane] = (uint16_t)t2;
+#endif
 #ifndef TLCG_NO_STORE  // (experiment only: measures what the records cost)
       __builtin_amdgcn_raw_buffer_store_b32(comp_record(t, head, action), rsrc,
                                             new1 ? (int)((unsigned)tail * 256u + loff) : OOB, 0, 0);
@@ -232,7 +336,11 @@ __device__ __forceinline__ void component_lane_body(const CompArgs& a, const Lay
                                             new2 ? (int)((unsigned)(tail + (new1 ? 1 : 0)) * 256u + loff) : OOB, 0,
                                             0);
 #endif
+#if TLCG_LANE_OWNER_RING
+      const uint32_t first_new = new1 ? o1 : o2;
+#else
       const ckey first_new = new1 ? t : t2;
+#endif
       tail += (new1 ? 1 : 0) + (new2 ? 1 : 0);
 #if TLCG_LANE_STEP_TAB
       const int nsucc = (e1 ? 1 : 0) + (e2 ? 1 : 0) + (alive ? selfloop_count_tab(L, term_c, term) : 0);  // + stutters
@@ -240,7 +348,7 @@ __device__ __forceinline__ void component_lane_body(const CompArgs& a, const Lay
       const int nsucc = (e1 ? 1 : 0) + (e2 ? 1 : 0) + (alive ? selfloop_count_c(L, ccon, s) : 0);  // + stutters
 #endif
       lvgen += (unsigned)nsucc;
-      if constexpr (OD) ocnt += alive ? 1u << (10 * (tail - tail0)) : 0u;  // new states this expansion discovered
+      if constexpr (OD) lgen += alive ? 256u << (8 * (tail - tail0)) : 0u;  // new states this expansion discovered
       // the inserted successors' invariants (first failing + 1; INV_UNKNOWN
       // + 1: the rare branch settles it -- a failing feature, or an outcome
       // table that left it to the programs)
@@ -319,20 +427,21 @@ __device__ __forceinline__ void component_lane_body(const CompArgs& a, const Lay
     const bool fin = act && !ovf;
     const int lvc = level < LV ? level : LV - 1;
     level_add(fin && tail > lvl_start && level >= counted, lvc, (uint32_t)(tail - lvl_start));
+    if constexpr (OD) {  // (every lane here: one wave sum and one LDS add per count, as level_add)
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        const u64 w = wave_sum_u64(fin ? (lgen >> (8 + 8 * i)) & 0xFFu : 0u);
+        if (lane == 0 && w) atomicAdd(&lvl_sh[LV + i], (unsigned long long)w);
+      }
+    }
     if (fin) {
-      gen += lgen;
+      gen += OD ? lgen & 0xFFu : lgen;
       dist += (uint32_t)tail;
       nexp += (uint32_t)head;
-      if constexpr (OD) {
-        od0 += ocnt & 1023;
-        od1 += (ocnt >> 10) & 1023;
-        od2 += ocnt >> 20;
-      }
       ev = min(ev, (unsigned long long)lev);
     }
   }
   const u64 g64 = wave_sum_u64(gen), d64 = wave_sum_u64(dist), x64 = wave_sum_u64(nexp);
-  const u64 o0 = wave_sum_u64(od0), o1 = wave_sum_u64(od1), o2 = wave_sum_u64(od2);
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) ev = min(ev, (unsigned long long)__shfl_xor(ev, off));
   __syncthreads();
@@ -342,12 +451,9 @@ __device__ __forceinline__ void component_lane_body(const CompArgs& a, const Lay
     if (g64) atomicAdd(&a.totals[so + 0], (unsigned long long)g64);
     if (d64) atomicAdd(&a.totals[so + 1], (unsigned long long)d64);
     if (ev != NO_EVENT) atomicMin(a.event, ev);
-    if constexpr (OD) {
-      if (o0) atomicAdd(&a.outdeg[so + 0], (unsigned long long)o0);
-      if (o1) atomicAdd(&a.outdeg[so + 1], (unsigned long long)o1);
-      if (o2) atomicAdd(&a.outdeg[so + 2], (unsigned long long)o2);
-    }
   }
+  if constexpr (OD)
+    if (lane < 3 && lvl_sh[LV + lane]) atomicAdd(&a.outdeg[so + lane], lvl_sh[LV + lane]);
   if (lane < LV && lvl_sh[lane]) {
     atomicAdd(&a.lvl[so + lane], lvl_sh[lane] & 0xffffffffull);
     if (lvl_sh[lane] >> 32) atomicAdd(&a.lvl_gen[so + lane], lvl_sh[lane] >> 32);

@@ -331,20 +331,23 @@ bool build_slot_owner(const HostModel& hm, int T, uint32_t mult, uint32_t dmult,
 }
 
 bool build_lane_phash(const HostModel& hm, uint32_t* mult, uint32_t* owner, std::string* why) {
-  std::fill(owner, owner + LANE_T, 0u);
+  std::fill(owner, owner + 2 * LANE_T, 0u);
   *mult = 0;
   const Layout& L = hm.L;
   if (L.producer || code_bits(L) > 16) return false;
   std::vector<std::vector<uint32_t>> calls;
   std::vector<uint32_t> codes;
   if (!comp0_calls(hm, 63, 1, &calls, &codes)) return false;  // (>= 63 states: past the pass's K = 64 - 2)
-  // an owner word is code + 1 in its low half and the code's invariant
-  // features in its top half (component_code.h lane_inv_feat), which the
-  // kernel ands with each component's mask: only if that is
+  // an owner entry is two words (component_code.h lane_owner_word): code + 1,
+  // the code's invariant features, which the kernel ands with each
+  // component's mask, and its step-table index in the first, its dense index
+  // in S (the position in `codes`) in the second.  The pass is taken only if
+  // every field fits, and the features only if they are
   // check_invariants_cb's answer on every code of S, under the constants of
   // the first components (tlcg_host_lane_inv_selfcheck: every code and class)
+  if (codes.size() > 62) return false;  // (a dense index is a bit of a 64-bit register)
   for (uint32_t c : codes) {
-    if (c + 1u > 0xFFFFu || lane_inv_feat(L, c) > 0xFFFFu) return false;
+    if (lane_owner_word(L, c) == 0u) return false;
     for (u64 idx = 0; idx < 16 && idx < hm.n_init && !hm.user; ++idx) {
       const CodeConsts kc = code_consts(L, comp_msgs_init(L, (u64)init_state<u128>(L, idx)));
       if (((lane_inv_feat(L, c) & lane_inv_mask(L, kc)) != 0) != (check_invariants_cb(L, kc, c) != -1)) {
@@ -355,7 +358,7 @@ bool build_lane_phash(const HostModel& hm, uint32_t* mult, uint32_t* owner, std:
       }
     }
   }
-  std::vector<uint32_t> used(LANE_T, 0);
+  std::vector<uint32_t> used(2 * LANE_T, 0);
   uint64_t x = 0x2545F4914F6CDD1Dull;  // a fixed sequence: the choice is deterministic
   for (int i = 0; i < (1 << 20); ++i) {
     x ^= x << 13;
@@ -364,13 +367,14 @@ bool build_lane_phash(const HostModel& hm, uint32_t* mult, uint32_t* owner, std:
     const uint32_t m = ((uint32_t)(x >> 20) & 0xFFFFFFu) | 1u;
     std::fill(used.begin(), used.end(), 0u);
     bool ok = true;
-    for (uint32_t c : codes) {
-      const unsigned sl = lane_slot(c, m);
-      if (used[sl]) {
+    for (size_t i = 0; i < codes.size(); ++i) {
+      const unsigned sl = lane_slot(codes[i], m);
+      if (used[2 * sl]) {
         ok = false;
         break;
       }
-      used[sl] = (c + 1u) | (lane_inv_feat(L, c) << 16);
+      used[2 * sl] = lane_owner_word(L, codes[i]);
+      used[2 * sl + 1] = (uint32_t)i;
     }
     if (ok) {
       *mult = m;
@@ -987,6 +991,84 @@ int64_t tlcg_host_lane_inv_selfcheck(const tlcg_model* m) {
       }
     }
   return checked;
+}
+
+// The per-lane kernel's owner table as build_lane_phash fills it (round 8),
+// entry by entry against S walked here on its own (component 0's FIFO BFS,
+// compactor_step_cb and crash_step_c): each code of S sits in its slot with
+// code + 1, lane_inv_feat and the step index in the first word -- the index
+// being the one compactor_step_tab computes, and the entry it selects giving
+// compactor_step_cb's successor, result and action -- and its BFS position in
+// the second, the positions a bijection onto 0..|S| - 1; every other slot is
+// empty.  *overflow (when given): a
+// field of some code of S does not fit its bits, by plain arithmetic (the
+// pass must then be refused).  Returns |S|, 0 when build_lane_phash refuses
+// the model, -(1 + position) of the first code that disagrees, -1 on a bad
+// model.
+int64_t tlcg_host_lane_owner_selfcheck(const tlcg_model* m, int* overflow) {
+  HostModel hm;
+  std::string e;
+  if (overflow) *overflow = 0;
+  if (!m || !build_model(*m, &hm, &e)) return -1;
+  const Layout& L = hm.L;
+  std::vector<uint32_t> owner(2 * LANE_T);
+  uint32_t mult = 0;
+  const bool taken = build_lane_phash(hm, &mult, owner.data(), nullptr);
+  if (L.producer || code_bits(L) > 16) return taken ? -1 : 0;
+  const u128 s0 = init_state<u128>(L, 0);
+  const CodeConsts kc = code_consts(L, comp_msgs_init(L, (u64)s0));
+  std::vector<uint32_t> q{code_encode_w<u128>(L, s0)};
+  std::unordered_set<uint32_t> seen{q[0]};
+  for (size_t head = 0; head < q.size() && q.size() <= 64; ++head) {
+    ckey t = 0, t2 = 0;
+    int act = 0;
+    if (compactor_step_cb(L, kc, q[head], &t, &act) == 1 && seen.insert(t).second) q.push_back(t);
+    if (crash_step_c(L, q[head], &t2) && seen.insert(t2).second) q.push_back(t2);
+  }
+  // the step index by plain arithmetic on the code's layout: phase, R, the largest ledger present
+  auto plain_index = [&](uint32_t c) {
+    uint32_t mx = 0;
+    for (int j = 0; j < L.C; ++j)
+      if ((c >> j) & 1u) mx = (uint32_t)j + 1u;
+    return ((c >> (L.C + 2)) & 7u) | (((c >> L.C) & 1u) << 3) | (mx << 4);
+  };
+  bool ovf = q.size() > 62;
+  for (uint32_t c : q)
+    if (c + 1u >= (1u << 16) || lane_inv_feat(L, c) >= (1u << 9) || plain_index(c) >= (1u << 6)) ovf = true;
+  if (overflow) *overflow = ovf ? 1 : 0;
+  if (!taken) return 0;
+  if (ovf) return -1;  // (taken although a field does not fit)
+  u64 tab[STEP_TAB];
+  for (int i = 0; i < STEP_TAB; ++i) tab[i] = compactor_step_entry(L, i);
+  std::vector<int> slot_used(LANE_T, 0);
+  u64 dense_seen = 0;
+  for (size_t i = 0; i < q.size(); ++i) {
+    const ckey c = q[i];
+    const unsigned sl = lane_slot(c, mult);
+    const uint32_t w = owner[2 * sl], d = owner[2 * sl + 1];
+    const uint32_t ix = w >> LANE_OWNER_STEP_SH;
+    ckey t = 0, t3 = 0;
+    int a1 = -1, a3 = -1;
+    const int r1 = compactor_step_cb(L, kc, c, &t, &a1);
+    const int r3 = ix < (uint32_t)STEP_TAB ? compactor_step_ent(L, kc, tab[ix], ix & 7u, c, &t3, &a3) : -1;
+    if (slot_used[sl]++ || (w & 0xFFFFu) != c + 1u || ((w >> LANE_OWNER_FEAT_SH) & 0x1FFu) != lane_inv_feat(L, c) ||
+        ix != plain_index(c) || r3 != r1 || (r1 == 1 && t3 != t) || (r1 && a3 != a1) || d != (uint32_t)i || d >= q.size() || ((dense_seen >> d) & 1))
+      return -(1 + (int64_t)i);
+    dense_seen |= 1ull << d;
+  }
+  if (dense_seen != (q.size() >= 64 ? ~0ull : (1ull << q.size()) - 1)) return -(1 + (int64_t)q.size());
+  for (int s = 0; s < LANE_T; ++s)
+    if (!slot_used[s] && (owner[2 * s] || owner[2 * s + 1])) return -(1 + (int64_t)q.size());
+  return (int64_t)q.size();
+}
+
+// word 0 of the owner entry of an arbitrary code (component_code.h
+// lane_owner_word; 0: a field does not fit), -1 on a bad model
+int64_t tlcg_host_lane_owner_word(const tlcg_model* m, uint32_t code) {
+  HostModel hm;
+  std::string e;
+  if (!m || !build_model(*m, &hm, &e)) return -1;
+  return (int64_t)lane_owner_word(hm.L, code);
 }
 
 }  // extern "C"

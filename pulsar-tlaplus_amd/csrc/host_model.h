@@ -80,12 +80,14 @@ bool build_slot_owner(const HostModel& hm, int T, uint32_t mult, uint32_t dmult,
 // the per-lane bitmap pass (component_lane.h): a 24-bit multiplier under
 // which lane_slot (the top 8 bits of code x mult) is injective on component
 // 0's code set -- without a Producer the code set every component shares --
-// and owner[s] = (the code in slot s + 1) | its invariant features << 16
-// (component_code.h lane_inv_feat; 0: no code), LANE_T entries.  The first
-// multiplier of a fixed sequence that works; false when the component has 63
-// or more states (the pass's capacity), no multiplier was found, or the
-// features and a component's mask do not give check_invariants_cb's answer on
-// a code of the set (the reason in *why)
+// and the owner table, LANE_T entries of two words: owner[2 s] = (the code in
+// slot s + 1) | its invariant features << 16 | its step-table index << 25
+// (component_code.h lane_owner_word; 0: no code), owner[2 s + 1] = the code's
+// dense index in the set (its BFS position).  The first multiplier of a fixed
+// sequence that works; false when the component has 63 or more states (the
+// pass's capacity), a field of some code's entry does not fit, no multiplier
+// was found, or the features and a component's mask do not give
+// check_invariants_cb's answer on a code of the set (the reason in *why)
 bool build_lane_phash(const HostModel& hm, uint32_t* mult, uint32_t* owner, std::string* why = nullptr);
 // the per-lane pass's FIFO ring entries (component_lane.h LANE_R, a hipRTC
 // define): the smallest power of 2 >= 8 whose ring holds component 0's widest

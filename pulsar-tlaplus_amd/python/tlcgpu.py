@@ -114,6 +114,8 @@ def load_library(path: str = LIB_PATH):
         "tlcg_host_check_invariants": (C.c_int, [M, U64]),
         "tlcg_host_component_selfcheck": (C.c_int64, [M, U64, U64]),
         "tlcg_host_lane_inv_selfcheck": (C.c_int64, [M]),
+        "tlcg_host_lane_owner_selfcheck": (C.c_int64, [M, C.POINTER(C.c_int)]),
+        "tlcg_host_lane_owner_word": (C.c_int64, [M, C.c_uint32]),
         "tlcg_host_tree_slot_probes": (C.c_int, [M, U64, C.POINTER(C.c_int64)]),
         "tlcg_host_termination_counterexample": (C.c_int64, [M]),
         "tlcg_owner": (C.c_int, [P, U64]),
@@ -340,6 +342,23 @@ def host_lane_inv_selfcheck(model: Model) -> int:
     the model; < 0: a disagreement)."""
     m = model.to_c()
     return load_library().tlcg_host_lane_inv_selfcheck(C.byref(m))
+
+
+def host_lane_owner_selfcheck(model: Model):
+    """(codes of S whose owner-table entry was verified field by field, whether
+    a field of some code of S does not fit).  The count is 0 when the per-lane
+    pass refuses the model, < 0 on a disagreement."""
+    m = model.to_c()
+    ovf = C.c_int(0)
+    n = load_library().tlcg_host_lane_owner_selfcheck(C.byref(m), C.byref(ovf))
+    return n, bool(ovf.value)
+
+
+def host_lane_owner_word(model: Model, code: int) -> int:
+    """The first word of the per-lane kernel's owner entry of `code`: code + 1
+    | features << 16 | step index << 25 (0: a field does not fit)."""
+    m = model.to_c()
+    return load_library().tlcg_host_lane_owner_word(C.byref(m), C.c_uint32(code))
 
 
 def host_tree_slot_probes(model: Model, comp: int):
