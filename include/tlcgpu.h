@@ -474,6 +474,91 @@ int tlcg_host_property_form(const tlcg_model* m, const char* name, int32_t* form
  * either (P is TRUE for the forms without one).  0, or < 0 as above. */
 int tlcg_host_property_eval(const tlcg_model* m, const char* name, const uint64_t* states, uint64_t n, uint8_t* out);
 
+/* ---- action properties: [][A]_v on one GPU --------------------------------
+ * A safety property over steps: every step s -> t of every behavior satisfies
+ * A \/ v' = v.  `name` is a definition of m->user_defs without parameters whose
+ * body, outer parentheses stripped, is [][A]_v: the tokens [] [ A ] and a
+ * subscript _name or _<<...>>, nothing after it.  v is a variable, a tuple
+ * << >> of such or a name defined as one (vars, bookieVars, compactorVars and
+ * otherVars are known where the definitions do not hold them), flattened to a
+ * set of variables.  A is an expression of the user-invariant subset with
+ *   x'           the variable x in the successor state, usable wherever x is
+ *                (messages'[i].key, Len(messages'), cursor' # cursor, ...);
+ *                the prime follows the variable's name directly;
+ *   UNCHANGED e  e of v's shape: the conjunction of x' = x over its variables;
+ * also inside LET bodies, quantifier bodies and the definitions A uses.  The
+ * program checked is A \/ UNCHANGED v, left to right: A is evaluated first and
+ * its evaluation error is an error.  Refused, with a message naming the
+ * definition, the line, the column and the construct, never checked
+ * approximately: a prime on anything but a variable's name ((e)', Name', x''),
+ * ENABLED, \cdot, WF_ / SF_, [] or <> inside A, <<A>>_v, text after the
+ * subscript, a subscript that is not variables, an A that is not boolean.
+ * Primes anywhere else (invariants, operands of <>, []<>, ~>) stay refused.
+ *
+ * The pass: the reach BFS of tlcg_check_property over the whole graph, then
+ * one kernel over the stored states that evaluates the program on every step
+ * (s, t), t a successor of s that differs from s, and counts steps, violating
+ * steps (FALSE) and erroring steps.  [TLC-ext] a successor equal to its state
+ * is not a step and is not evaluated (v' = v holds there); TLC evaluates A
+ * first on such a successor too, so an A that fails to evaluate only on
+ * stuttering steps is an error in TLC and passes here.
+ * The reported step, whatever order the device stored the states in: among
+ * the states with a violating or erroring step, the ones of the shallowest BFS
+ * level; of those the least packed state; of that state the lowest-numbered
+ * move (Next order) that violates or errs.  If that step errs the call returns
+ * -7 with error_state set and the trace filled; else it is the violation.
+ * The trace is the BFS path from Init to s (a shortest one), then t:
+ * actions[i] is the TLCG_ACT_* of the step into states[i]; no loop, no
+ * stuttering tail.  [TLC-ext] TLC checks such a property inside its BFS and
+ * stops at the first violation it meets, so its counts and its trace's last
+ * step may differ; holds / violated and the level of the step agree.
+ * An evaluation error of the spec's own step is -6, as in tlcg_check_property.
+ * At most 2^32 - 1 reachable states.  Returns as tlcg_check_property. */
+typedef struct tlcg_action_property {
+  int32_t holds;
+  int32_t depth;        /* levels of the reachable graph */
+  uint64_t reachable;
+  uint64_t steps;       /* steps evaluated: edges s -> t with t # s */
+  uint64_t violating;
+  uint64_t erroring;
+  int32_t step_depth;   /* level of the reported step's source (Init is level 1), 0 when it holds */
+  int32_t step_action;  /* TLCG_ACT_* of the reported step, -1 when it holds */
+  int32_t trace_len;
+  int32_t reserved;
+  int64_t error_state;  /* -1, else the store index of the reported erroring step's source */
+  double kernel_ms;     /* device time of both phases */
+  double check_ms;      /* phase 2 (the step kernel) alone */
+  double wall_ms;
+} tlcg_action_property;
+int tlcg_check_action_property(const tlcg_model* m, const tlcg_opts* o, const char* name, tlcg_action_property* out,
+                               uint64_t* states, int32_t* actions, int32_t cap, int32_t* len, char* err,
+                               int32_t err_cap);
+/* Self-test of the step pass on a caller's CSR graph (as
+ * tlcg_property_graph_selftest): the reach BFS, the step kernel and the pick,
+ * with the verdict of edge e = row[v] + k taken from verdict[e] (0 holds, 1
+ * violates, 2 errs) instead of the interpreter; an edge back to its own node is
+ * not a step.  words = 1 or 2.  A reported erroring step comes back as rc 0
+ * with error_state set (holds = 0).  Actions are edge ordinals. */
+int tlcg_action_property_graph_selftest(const uint32_t* row, const uint32_t* col, const uint8_t* verdict, uint32_t n,
+                                        uint32_t n_init, int32_t words, const tlcg_opts* o,
+                                        tlcg_action_property* out, uint64_t* states, int32_t* actions, int32_t cap,
+                                        int32_t* len, char* err, int32_t err_cap);
+/* The front end alone, on the host: 0 with *var_mask = the flattened subscript,
+ * a bit per variable in declaration order (messages, compactedLedgers, cursor,
+ * compactorState, phaseOneResult, compactionHorizon, compactedTopicContext,
+ * crashTimes, consumeTimes); -1 refused (message in err); -2 the body does not
+ * start with [][ (not an action property); -3 no such definition or a bad
+ * model. */
+int tlcg_host_action_property_form(const tlcg_model* m, const char* name, uint32_t* var_mask, char* err, int32_t cap);
+/* The compiled program on n pairs (s, t) of tlcg_state_words words each
+ * (pairs[2 i] = s, pairs[2 i + 1] = t), by the host interpreter: out[i] = 0
+ * TRUE, 1 FALSE, 2 evaluation error.  0, or < 0 as above. */
+int tlcg_host_action_property_eval(const tlcg_model* m, const char* name, const uint64_t* pairs, uint64_t n,
+                                   uint8_t* out);
+/* Test hook: the same on the device, one lane per pair. */
+int tlcg_action_eval_selftest(const tlcg_model* m, const tlcg_opts* o, const char* name, const uint64_t* pairs,
+                              uint64_t n, uint8_t* out, char* err, int32_t cap);
+
 /* Enable xGMI peer access among devices 0..n-1 (one process driving contexts
  * on several devices, e.g. tlc-hip -gpus N).  Returns the pairs enabled. */
 int tlcg_peer_access(int32_t n);

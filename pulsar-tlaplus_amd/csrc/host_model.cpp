@@ -759,6 +759,40 @@ int tlcg_host_property_eval(const tlcg_model* m, const char* name, const uint64_
   return 0;
 }
 
+int tlcg_host_action_property_form(const tlcg_model* m, const char* name, uint32_t* var_mask, char* err,
+                                   int32_t cap) {
+  auto fail = [&](int rc, const std::string& e) {
+    if (err && cap > 0) std::snprintf(err, (size_t)cap, "%s", e.c_str());
+    return rc;
+  };
+  HostModel hm;
+  std::string e;
+  if (!m || !name) return fail(-3, "null argument");
+  if (!build_model(*m, &hm, &e)) return fail(-3, e);
+  uint32_t mask = 0;
+  const int rc = compile_action_property(*m, hm, name, &mask, nullptr, &e);
+  if (rc) return fail(rc, e);
+  if (var_mask) *var_mask = mask;
+  if (err && cap > 0) err[0] = 0;
+  return 0;
+}
+
+int tlcg_host_action_property_eval(const tlcg_model* m, const char* name, const uint64_t* pairs, uint64_t n,
+                                   uint8_t* out) {
+  HostModel hm;
+  std::string e;
+  if (!m || !name || (n && (!pairs || !out)) || !build_model(*m, &hm, &e)) return -3;
+  const std::unique_ptr<UserProg> prog(new UserProg);
+  const int rc = compile_action_property(*m, hm, name, nullptr, prog.get(), &e);
+  if (rc) return rc;
+  const int w = state_words(hm.L);
+  for (uint64_t i = 0; i < n; ++i) {
+    const u128 s = join_words(pairs + 2 * i * (uint64_t)w, w), t = join_words(pairs + (2 * i + 1) * (uint64_t)w, w);
+    out[i] = (uint8_t)eval_user2<u128>(hm.L, *prog, 0, s, t);
+  }
+  return 0;
+}
+
 int tlcg_host_check_invariants(const tlcg_model* m, uint64_t state) {
   HostModel hm;
   std::string e;

@@ -37,6 +37,16 @@ std::vector<std::string> user_def_names(const char* text);
 // state predicate); -3 when there is no such definition.
 int compile_property(const tlcg_model& m, const HostModel& hm, const std::string& name, int* form, UserProg* P,
                      std::string* err);
+// The action front end (user_inv.cpp): definition `name` of m.user_defs as a
+// safety property over steps, [][A]_v, compiled into *P as entry 0 = A \/
+// UNCHANGED v, a two-state program (user_inv.h eval_user2_v); *var_mask = v
+// flattened, a bit per variable in declaration order.  P == nullptr: the front
+// end alone.  0; -1 refused, with a message naming the definition, the line,
+// the column and the construct; -2 when the body does not start with [][ (not
+// an action property: compile_property's business); -3 when there is no such
+// definition or the model is bad.
+int compile_action_property(const tlcg_model& m, const HostModel& hm, const std::string& name, uint32_t* var_mask,
+                            UserProg* P, std::string* err);
 // The compiled user invariants as device code for the run-time specialized
 // kernels (user_inv.cpp; model.h tlcg_user_eval), one function per invariant.
 // With the layout: the per-component outcome tables of the invariants that

@@ -1539,3 +1539,418 @@ extern "C" int tlcg_property_graph_selftest(const uint32_t* row, const uint32_t*
   pp_copy_out(tr, words, out, states, actions, cap, len);
   return 0;
 }
+
+// ---------------------------------------------------------------- action properties
+// [][A]_v over a compiled two-state program (tlcgpu.h
+// tlcg_check_action_property): a safety property over steps, so there is no
+// G', no seed and no cycle -- every step of the reachable graph is looked at
+// once.
+//   1. reach: the BFS above over the whole graph (ReachAll), which leaves the
+//      level-contiguous store and the parent log;
+//   2. check (k_ap_check): one lane per stored state; every move that changes
+//      the state is a step (the graph policy's definition; [TLC-ext] TLC would
+//      evaluate A on a stuttering successor as well) and is evaluated on
+//      (s, t) -- the successor is recomputed, never looked up.  Steps,
+//      violating and erroring steps are counted in registers and added once
+//      per wave; a flag byte per state says whether it has a violating (bit
+//      0) or an erroring (bit 1) step;
+//   3. the reported step, independent of the order the races of phase 1 left
+//      in the store: the least flagged stored index names the shallowest level
+//      with a flagged state (the store is level-contiguous), k_lv_pick takes
+//      the least packed flagged state of that level, and the host takes that
+//      state's lowest-numbered flagged move.
+// Beside the reach pass's buffers: nothing per state -- the flag byte is the
+// reach pass's stuck byte, which this pass has no other use for.
+namespace {
+
+enum ApFlag { AP_VIOLATES = 1, AP_ERRS = 2 };
+
+struct ApCtr {
+  unsigned long long steps, violating, erroring;
+  unsigned long long first;  // least stored index of a flagged state
+};
+
+// the verdict of a step (0 holds, 1 violates, 2 errs): by the compiled program ...
+template <typename W>
+struct ProgStep {
+  Layout L;
+  const UserProg* prog;  // device memory in the kernels' instance, host memory in the host's
+  TLCG_HDM int verdict(W s, int, W t) const { return eval_user2<W>(L, *prog, 0, s, t); }
+};
+// ... or, for an explicit graph, by the caller's byte per edge
+template <typename W>
+struct ByteStep {
+  const uint32_t* row;
+  const unsigned char* v;
+  TLCG_HDM int verdict(W s, int k, W) const { return v[row[ExplicitGraph<W>::node_of(s)] + (uint32_t)k]; }
+};
+
+template <typename R, typename E>
+__global__ __launch_bounds__(LV_BLOCK) void k_ap_check(LvBufs<R> B, E ev, u64 n, ApCtr* ctr) {
+  using W = typename R::word;
+  const R& gr = B.g;
+  const int kmax = gr.moves_bound();
+  const u64 stride = (u64)gridDim.x * LV_BLOCK;
+  u64 steps = 0, viol = 0, errs = 0;
+  bool seen = false;  // (wave-uniform: later chunks hold larger indices)
+  for (u64 base = (u64)blockIdx.x * LV_BLOCK; base < n; base += stride) {
+    const u64 g = base + threadIdx.x;
+    unsigned f = 0;
+    if (g < n) {
+      const W s = B.store[g];
+      for (int k = 0; k < kmax; ++k) {
+        W t = 0;
+        int ord = 0;
+        if (gr.move(s, k, &t, &ord) != 1) continue;  // (2: the reach pass has reported it)
+        ++steps;
+        const int v = ev.verdict(s, k, t);
+        if (v == 1) {
+          ++viol;
+          f |= AP_VIOLATES;
+        } else if (v != 0) {
+          ++errs;
+          f |= AP_ERRS;
+        }
+      }
+      B.stuck[g] = (unsigned char)f;
+    }
+    if (!seen && __ballot(f != 0)) {
+      wave_first(f != 0, g, &ctr->first);
+      seen = true;
+    }
+  }
+  const u64 st = wave_sum_u64(steps), vi = wave_sum_u64(viol), er = wave_sum_u64(errs);
+  if (__lane_id() == 0) {
+    if (st) atomicAdd(&ctr->steps, (unsigned long long)st);
+    if (vi) atomicAdd(&ctr->violating, (unsigned long long)vi);
+    if (er) atomicAdd(&ctr->erroring, (unsigned long long)er);
+  }
+}
+
+// dg / hg: the graph as the kernels / the host read it; dev / host: the step
+// evaluator likewise.  -7: the reported step errs (out->error_state, *tr filled).
+template <typename G, typename E>
+int run_action(const G& dg0, const G& hg0, const E& dev, const E& host, const tlcg_opts* o, tlcg_action_property* out,
+               LvTrace* tr, std::string* err) {
+  using R = ReachAll<G>;
+  using W = typename G::word;
+  const R dg{dg0}, hg{hg0};
+  const unsigned grid_cap = lv_grid_cap();
+  auto grid_for = [grid_cap](u64 n) { return lv_grid(n, grid_cap); };
+  u64 cap = o && o->state_capacity ? o->state_capacity : (u64)1 << 22;
+  int log2 = o && o->log2_fpset_slots > 0 ? o->log2_fpset_slots : 0;
+  hipEvent_t e0, e1;
+  LV_CHECK(hipEventCreate(&e0));
+  LV_CHECK(hipEventCreate(&e1));
+  struct EvGuard {
+    hipEvent_t a, b;
+    ~EvGuard() {
+      hipEventDestroy(a);
+      hipEventDestroy(b);
+    }
+  } evg{e0, e1};
+  for (int attempt = 0;; ++attempt) {
+    if (cap >= (1ull << 32) - 1) {
+      *err = "the action property check indexes states with 32 bits: more than 2^32 - 1 reachable states";
+      return -5;
+    }
+    int lg = log2;
+    if (lg <= 0 || attempt > 0) {
+      lg = 10;
+      while ((1ull << lg) < 2 * cap) ++lg;
+    }
+    if (lg > 32) lg = 32;
+    DevMem mem;
+    LvBufs<R> B;
+    B.g = dg;
+    B.log2 = lg;
+    B.cap = cap;
+    const u64 nslots = 1ull << lg;
+    ApCtr* d_ctr = nullptr;
+    // 1. reach
+    if (!mem.alloc(&B.slots, nslots * (sizeof(W) / 8)) || !mem.alloc(&B.store, cap) || !mem.alloc(&B.parent, cap) ||
+        !mem.alloc(&B.slot_of, cap) || !mem.alloc(&B.gidx_of, nslots) || !mem.alloc(&B.indeg, nslots) ||
+        !mem.alloc(&B.stuck, cap) || !mem.alloc(&B.ctr, 1) || !mem.alloc(&d_ctr, 1)) {
+      if (cap > (1ull << 20) && attempt < 8) {
+        cap /= 2;
+        log2 = 0;
+        continue;
+      }
+      *err = "action property: device allocation failed (" + std::to_string(cap) + " states, 2^" +
+             std::to_string(lg) + " FPSet slots)";
+      return -5;
+    }
+    LV_CHECK(hipMemset(B.slots, 0, nslots * sizeof(W)));
+    LV_CHECK(hipMemset(B.indeg, 0, nslots * sizeof(u32)));
+    LvCtr h{};
+    h.first_init = ~0ull;
+    LV_CHECK(hipMemcpy(B.ctr, &h, sizeof h, hipMemcpyHostToDevice));
+    auto read_ctr = [&]() -> int {
+      LV_CHECK(hipMemcpy(&h, B.ctr, sizeof h, hipMemcpyDeviceToHost));
+      return 0;
+    };
+    float ms = 0.f;
+    LV_CHECK(hipEventRecord(e0, 0));
+    k_lv_init<R><<<grid_for(hg.n_init()), LV_BLOCK>>>(B);
+    LV_CHECK(hipGetLastError());
+    if (read_ctr()) return -4;
+    std::vector<u64> level_base{0, std::min<u64>(h.n, cap)};
+    bool again = (h.flags & (LV_FPSET | LV_STORE)) != 0;
+    while (!again && level_base.back() > level_base[level_base.size() - 2]) {
+      const u64 a = level_base[level_base.size() - 2], b = level_base.back();
+      k_lv_expand<R><<<grid_for(b - a), LV_BLOCK>>>(B, a, b, TLCG_FAIR_WF_NEXT);
+      LV_CHECK(hipGetLastError());
+      if (read_ctr()) return -4;
+      if (h.flags & LV_EVAL) {
+        *err = "action property: an evaluation error while computing a successor (run the safety check first)";
+        return -6;
+      }
+      if ((again = (h.flags & (LV_FPSET | LV_STORE)) != 0)) break;
+      level_base.push_back(h.n);
+    }
+    LV_CHECK(hipEventRecord(e1, 0));
+    LV_CHECK(hipEventSynchronize(e1));
+    LV_CHECK(hipEventElapsedTime(&ms, e0, e1));
+    if (again) {
+      cap *= 4;
+      continue;  // redo with a larger store and FPSet
+    }
+    const u64 n = h.n;
+    out->reachable = n;
+    out->depth = (int32_t)(level_base.size() - 2);
+    out->kernel_ms = ms;
+    // 2. check
+    ApCtr c{};
+    c.first = ~0ull;
+    LV_CHECK(hipMemcpy(d_ctr, &c, sizeof c, hipMemcpyHostToDevice));
+    LV_CHECK(hipEventRecord(e0, 0));
+    k_ap_check<R, E><<<grid_for(n), LV_BLOCK>>>(B, dev, n, d_ctr);
+    LV_CHECK(hipGetLastError());
+    LV_CHECK(hipEventRecord(e1, 0));
+    LV_CHECK(hipEventSynchronize(e1));
+    LV_CHECK(hipEventElapsedTime(&ms, e0, e1));
+    LV_CHECK(hipMemcpy(&c, d_ctr, sizeof c, hipMemcpyDeviceToHost));
+    out->check_ms = ms;
+    out->kernel_ms += ms;
+    out->steps = c.steps;
+    out->violating = c.violating;
+    out->erroring = c.erroring;
+    if (c.first == ~0ull) {
+      out->holds = 1;
+      return 0;
+    }
+    // 3. the reported step
+    out->holds = 0;
+    if (c.first >= n) {
+      *err = "action property: the first flagged state lies outside the store";
+      return -6;
+    }
+    size_t lv = 0;
+    while (level_base[lv + 1] <= c.first) ++lv;
+    const u64 a = level_base[lv], b = level_base[lv + 1];
+    h.key_hi = h.key_lo = ~0ull;
+    h.pick = ~0ull;
+    LV_CHECK(hipMemcpy(B.ctr, &h, sizeof h, hipMemcpyHostToDevice));
+    for (int ph = 0; ph < 3; ++ph) k_lv_pick<R><<<grid_for(b - a), LV_BLOCK>>>(B, a, b, ph);
+    LV_CHECK(hipGetLastError());
+    if (read_ctr()) return -4;
+    if (h.pick < a || h.pick >= b) {
+      *err = "action property: no flagged state found in its level";
+      return -6;
+    }
+    W s;
+    LV_CHECK(hipMemcpy(&s, B.store + h.pick, sizeof(W), hipMemcpyDeviceToHost));
+    const int kmax = hg.moves_bound();
+    for (int k = 0; k < kmax; ++k) {
+      W t = 0;
+      int ord = 0;
+      if (hg.move(s, k, &t, &ord) != 1) continue;
+      const int v = host.verdict(s, k, t);
+      if (v == 0) continue;
+      out->step_depth = (int32_t)lv + 1;  // (levels count from 1, as depth does: Init is level 1)
+      out->step_action = hg.action_of(ord);
+      if (const int rc = path_to(B, hg, h.pick, tr, err)) return rc;
+      tr->states.push_back((u128)t);
+      tr->actions.push_back(out->step_action);
+      if (v != 1) {
+        out->error_state = (int64_t)h.pick;
+        return -7;
+      }
+      return 0;
+    }
+    *err = "action property: the host finds no violating step of the state the device flagged";
+    return -6;
+  }
+}
+
+void ap_reset(tlcg_action_property* out) {
+  std::memset(out, 0, sizeof *out);
+  out->step_action = -1;
+  out->error_state = -1;
+}
+
+void ap_copy_out(const LvTrace& tr, int words, tlcg_action_property* out, uint64_t* states, int32_t* actions,
+                 int32_t cap, int32_t* len) {
+  out->trace_len = (int32_t)tr.states.size();
+  if (states && actions && len) {
+    const int32_t n = std::min<int32_t>(cap, out->trace_len);
+    for (int32_t i = 0; i < n; ++i) {
+      split_words(tr.states[i], states + (size_t)i * words, words);
+      actions[i] = tr.actions[i];
+    }
+    *len = n;
+  }
+}
+
+template <typename W>
+int run_model_action(const HostModel& hm, const UserProg* h_prog, const UserProg* d_prog, const tlcg_opts* o,
+                     tlcg_action_property* out, LvTrace* tr, std::string* err) {
+  ModelGraph<W> g;
+  g.L = hm.L;
+  g.n_init_ = hm.n_init;
+  return run_action(g, g, ProgStep<W>{hm.L, d_prog}, ProgStep<W>{hm.L, h_prog}, o, out, tr, err);
+}
+
+template <typename W>
+int run_explicit_action(const uint32_t* row, const uint32_t* col, const uint8_t* verdict, uint32_t n, uint32_t n_init,
+                        const tlcg_opts* o, tlcg_action_property* out, LvTrace* tr, std::string* err) {
+  ExplicitGraph<W> hg{};
+  if (!explicit_graph_shape(row, col, n, n_init, &hg, err)) return -1;
+  hg.row = row;
+  hg.col = col;
+  hg.p = nullptr;  // (ReachAll asks for no P)
+  DevMem mem;
+  uint32_t *d_row = nullptr, *d_col = nullptr;
+  unsigned char* d_v = nullptr;
+  if (!mem.alloc(&d_row, (u64)n + 1) || !mem.alloc(&d_col, row[n]) || !mem.alloc(&d_v, row[n])) {
+    *err = "graph: device allocation failed";
+    return -5;
+  }
+  LV_CHECK(hipMemcpy(d_row, row, ((size_t)n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
+  if (row[n]) LV_CHECK(hipMemcpy(d_col, col, (size_t)row[n] * sizeof(uint32_t), hipMemcpyHostToDevice));
+  if (row[n]) LV_CHECK(hipMemcpy(d_v, verdict, row[n], hipMemcpyHostToDevice));
+  ExplicitGraph<W> dg = hg;
+  dg.row = d_row;
+  dg.col = d_col;
+  return run_action(dg, hg, ByteStep<W>{d_row, d_v}, ByteStep<W>{row, verdict}, o, out, tr, err);
+}
+
+// tlcg_action_eval_selftest: the program on pair i, one lane each
+template <typename W>
+__global__ __launch_bounds__(LV_BLOCK) void k_ap_eval(Layout L, const UserProg* prog, const u64* pairs, u64 n,
+                                                      unsigned char* out) {
+  constexpr int w = sizeof(W) / 8;
+  const u64 stride = (u64)gridDim.x * LV_BLOCK;
+  for (u64 i = (u64)blockIdx.x * LV_BLOCK + threadIdx.x; i < n; i += stride) {
+    W s = (W)pairs[2 * i * w], t = (W)pairs[(2 * i + 1) * w];
+    if constexpr (w == 2) {
+      s |= (W)pairs[2 * i * w + 1] << 64;
+      t |= (W)pairs[(2 * i + 1) * w + 1] << 64;
+    }
+    out[i] = (unsigned char)eval_user2<W>(L, *prog, 0, s, t);
+  }
+}
+
+}  // namespace
+
+extern "C" int tlcg_check_action_property(const tlcg_model* m, const tlcg_opts* o, const char* name,
+                                          tlcg_action_property* out, uint64_t* states, int32_t* actions, int32_t cap,
+                                          int32_t* len, char* err, int32_t err_cap) {
+  auto fail = [&](int rc, const std::string& e) {
+    if (err && err_cap > 0) std::snprintf(err, (size_t)err_cap, "%s", e.c_str());
+    return rc;
+  };
+  if (!m || !out || !name) return fail(-1, "null argument");
+  ap_reset(out);
+  if (len) *len = 0;
+  HostModel hm;
+  std::string e;
+  if (!build_model(*m, &hm, &e)) return fail(-3, e);
+  const std::unique_ptr<UserProg> prog(new UserProg);
+  if (compile_action_property(*m, hm, name, nullptr, prog.get(), &e) != 0) return fail(-2, e);
+  if (hipSetDevice(o ? o->device : 0) != hipSuccess) return fail(-4, "hipSetDevice failed");
+  const auto t0 = std::chrono::steady_clock::now();
+  DevMem mem;
+  UserProg* d_prog = nullptr;
+  if (!mem.alloc(&d_prog, 1) ||
+      hipMemcpy(d_prog, prog.get(), sizeof(UserProg), hipMemcpyHostToDevice) != hipSuccess)
+    return fail(-5, "action property: device allocation failed (the program)");
+  LvTrace tr;
+  const int words = state_words(hm.L);
+  const int rc = words == 1 ? run_model_action<u64>(hm, prog.get(), d_prog, o, out, &tr, &e)
+                            : run_model_action<u128>(hm, prog.get(), d_prog, o, out, &tr, &e);
+  out->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (rc == -7)
+    e = std::string("evaluating the action of property ") + name +
+        " failed on a step of a reachable state (the last two states of the trace)";
+  else if (rc)
+    return fail(rc, e);
+  ap_copy_out(tr, words, out, states, actions, cap, len);
+  return rc ? fail(rc, e) : 0;
+}
+
+extern "C" int tlcg_action_property_graph_selftest(const uint32_t* row, const uint32_t* col, const uint8_t* verdict,
+                                                   uint32_t n, uint32_t n_init, int32_t words, const tlcg_opts* o,
+                                                   tlcg_action_property* out, uint64_t* states, int32_t* actions,
+                                                   int32_t cap, int32_t* len, char* err, int32_t err_cap) {
+  auto fail = [&](int rc, const std::string& e) {
+    if (err && err_cap > 0) std::snprintf(err, (size_t)err_cap, "%s", e.c_str());
+    return rc;
+  };
+  if (!row || !out) return fail(-1, "null argument");
+  if (words != 1 && words != 2) return fail(-1, "words must be 1 or 2");
+  if (row[n] && (!col || !verdict)) return fail(-1, "null argument");
+  ap_reset(out);
+  if (len) *len = 0;
+  std::string e;
+  {  // a malformed graph is refused before the device is touched
+    ExplicitGraph<u64> shape{};
+    if (!explicit_graph_shape(row, col, n, n_init, &shape, &e)) return fail(-1, e);
+  }
+  if (hipSetDevice(o ? o->device : 0) != hipSuccess) return fail(-4, "hipSetDevice failed");
+  const auto t0 = std::chrono::steady_clock::now();
+  LvTrace tr;
+  int rc = words == 1 ? run_explicit_action<u64>(row, col, verdict, n, n_init, o, out, &tr, &e)
+                      : run_explicit_action<u128>(row, col, verdict, n, n_init, o, out, &tr, &e);
+  out->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (rc == -7) rc = 0;  // (error_state says so)
+  if (rc) return fail(rc, e);
+  ap_copy_out(tr, words, out, states, actions, cap, len);
+  return 0;
+}
+
+extern "C" int tlcg_action_eval_selftest(const tlcg_model* m, const tlcg_opts* o, const char* name,
+                                         const uint64_t* pairs, uint64_t n, uint8_t* out, char* err, int32_t cap) {
+  auto fail = [&](int rc, const std::string& e) {
+    if (err && cap > 0) std::snprintf(err, (size_t)cap, "%s", e.c_str());
+    return rc;
+  };
+  if (!m || !name || (n && (!pairs || !out))) return fail(-1, "null argument");
+  HostModel hm;
+  std::string e;
+  if (!build_model(*m, &hm, &e)) return fail(-3, e);
+  const std::unique_ptr<UserProg> prog(new UserProg);
+  if (compile_action_property(*m, hm, name, nullptr, prog.get(), &e) != 0) return fail(-2, e);
+  if (n == 0) return 0;
+  if (hipSetDevice(o ? o->device : 0) != hipSuccess) return fail(-4, "hipSetDevice failed");
+  const int words = state_words(hm.L);
+  DevMem mem;
+  UserProg* d_prog = nullptr;
+  u64* d_pairs = nullptr;
+  unsigned char* d_out = nullptr;
+  const u64 nw = 2 * n * (u64)words;
+  if (!mem.alloc(&d_prog, 1) || !mem.alloc(&d_pairs, nw) || !mem.alloc(&d_out, n))
+    return fail(-5, "action eval: device allocation failed");
+  auto run = [&](std::string* err) -> int {
+    LV_CHECK(hipMemcpy(d_prog, prog.get(), sizeof(UserProg), hipMemcpyHostToDevice));
+    LV_CHECK(hipMemcpy(d_pairs, pairs, nw * sizeof(u64), hipMemcpyHostToDevice));
+    const unsigned grid = lv_grid(n, lv_grid_cap());
+    if (words == 1) k_ap_eval<u64><<<grid, LV_BLOCK>>>(hm.L, d_prog, d_pairs, n, d_out);
+    else k_ap_eval<u128><<<grid, LV_BLOCK>>>(hm.L, d_prog, d_pairs, n, d_out);
+    LV_CHECK(hipGetLastError());
+    LV_CHECK(hipMemcpy(out, d_out, n, hipMemcpyDeviceToHost));
+    return 0;
+  };
+  const int rc = run(&e);
+  return rc ? fail(rc, e) : 0;
+}

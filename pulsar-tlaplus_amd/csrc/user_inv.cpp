@@ -22,6 +22,8 @@
 // Cardinality, DOMAIN, Head, Nat, Int, BOOLEAN, and every definition of the
 // module (by substitution, as TLA+ operators are).  Anything else is refused
 // with a message naming it; an invariant is never checked approximately.
+// An action property [][A]_v (compile_action_property, below) adds x' on a
+// variable and UNCHANGED e to this language, for A alone.
 //
 // Static typing resolves composites at compile time; what is left is 64-bit
 // integer work (user_inv.h).  TLC's evaluation order is kept where it decides
@@ -166,7 +168,9 @@ typedef std::shared_ptr<Node> NodeP;
 struct Node {
   enum K {
     NUM, BOOL, STR, ID, OPAPP, BIN, UN, IF, LET, QUANT, CHOOSE, SETENUM, SETFILTER, SETMAP, APP, FIELD, RECORD,
-    RECSET, FCTOR, TUPLE, JUNCT, DOMAIN, CASE
+    RECSET, FCTOR, TUPLE, JUNCT, DOMAIN, CASE,
+    PRIME,     // x' (c[0]: the variable's ID); action properties only
+    UNCHANGED  // UNCHANGED e (c[0]: a variable, a tuple of such, or a name defined as one)
   } k;
   std::string s;                     // name, operator, field, quantifier (\A / \E), junction (/\ or \/)
   long long v = 0;
@@ -191,7 +195,9 @@ std::string where(int line, int col) {
 // ---------------------------------------------------------------- parser
 class Parser {
  public:
-  explicit Parser(std::vector<Tok> t) : t_(std::move(t)) {}
+  // action: the text may hold x' and UNCHANGED (an action property's A and
+  // the definitions it uses, compile_action_property)
+  explicit Parser(std::vector<Tok> t, bool action = false) : t_(std::move(t)), action_(action) {}
 
   NodeP parse_all() {
     NodeP e = expr(0);
@@ -201,6 +207,7 @@ class Parser {
 
  private:
   std::vector<Tok> t_;
+  bool action_ = false;
   size_t p_ = 0;
   std::vector<int> fence_;  // columns of the enclosing bulleted lists: a token at or left of one ends the item
 
@@ -321,7 +328,15 @@ class Parser {
         f->c = {e};
         e = f;
       } else if (is("'")) {
-        fail("primed variables are not state predicates");
+        if (!action_) fail("primed variables are not state predicates");
+        if (e->k == Node::PRIME) fail("a double prime ('')");
+        if (e->k != Node::ID) fail("a prime (') on something that is not a variable's name");
+        const Tok at = next();
+        NodeP pr = mk(Node::PRIME, at);
+        pr->line = e->line;
+        pr->col = e->col;
+        pr->c = {e};
+        e = pr;
       } else {
         return e;
       }
@@ -390,13 +405,15 @@ class Parser {
     }
     if (t.k == Tok::OP && (t.s == "/\\" || t.s == "\\/" || t.s == "\\land" || t.s == "\\lor")) return junction();
     if (t.k == Tok::OP && (t.s == "[]" || (t.s == "<" && peek(1).k == Tok::OP && peek(1).s == ">")))
-      fail("a temporal formula ([] or <>) is not a state predicate");
+      fail(action_ ? "a temporal operator ([] or <>) inside the action of [][A]_v"
+                   : "a temporal formula ([] or <>) is not a state predicate");
     if (t.k == Tok::OP && t.s == "(") {
       ++p_;
       fence_.push_back(-1);  // parentheses lift the bullet fence
       NodeP e = expr(0);
       fence_.pop_back();
       expect(")");
+      if (is("'")) fail(action_ ? "a prime (') on a parenthesised expression" : "primed variables are not state predicates");
       return e;
     }
     if (t.k == Tok::OP && (t.s == "\\A" || t.s == "\\E" || t.s == "\\forall" || t.s == "\\exists")) {
@@ -486,9 +503,15 @@ class Parser {
         n->c = {postfix(primary())};
         return n;
       }
+      if (t.s == "UNCHANGED" && action_) {
+        const Tok at = next();
+        NodeP n = mk(Node::UNCHANGED, at);
+        n->c = {primary()};
+        return n;
+      }
       if (t.s == "LAMBDA" || t.s == "EXCEPT" || t.s == "SUBSET" || t.s == "UNION" || t.s == "ENABLED" ||
           t.s == "UNCHANGED")
-        fail("'" + t.s + "' is not supported in an invariant");
+        fail("'" + t.s + "' is not supported in " + (action_ ? "an action property" : "an invariant"));
       const Tok at = next();
       if (is("(")) {  // operator application Name(args)
         ++p_;
@@ -650,6 +673,7 @@ struct Val {
   NodeP node;                   // T_SET / T_FUNC: the expression, and its environment
   EnvP env;
   bool nil_literal = false;     // T_MV: the constant Nil
+  bool nx = false;              // SEQ / LEDGERS / P1R / LFK: its messages are the successor state's (x')
 };
 
 struct Bind {
@@ -680,9 +704,31 @@ struct Env : std::enable_shared_from_this<Env> {
 
 class Compiler {
  public:
-  Compiler(const HostModel& hm, UserProg* P) : L_(hm.L), P_(P) {}
+  Compiler(const HostModel& hm, UserProg* P, bool action = false) : L_(hm.L), P_(P), action_(action) {}
 
   std::map<std::string, Def> defs;
+
+  // compiles A \/ UNCHANGED v as entry k (an action property [][A]_v: d holds
+  // A's text, sub the subscript's); *var_mask = v's variables, a bit each in
+  // declaration order
+  void compile_action(int k, Def& d, Def& sub, const std::string& what, const std::string& at, uint32_t* var_mask) {
+    P_->entry[k] = pc();
+    nreg_ = 0;
+    EnvP env = std::make_shared<Env>();
+    uint32_t mask = 0;
+    const NodeP sn = body_of(sub);
+    flatten_vars(sn, env, &mask, "the subscript of " + what);
+    if (var_mask) *var_mask = mask;
+    const int res = R();
+    const Val a = lower(body_of(d), env);
+    if (a.t != T_BOOL) throw CompileError("the action of " + what + " is a " + tk_name(a.t) + ", not a boolean" + at);
+    emit(U_MOV, res, a.r[0]);
+    const int j = emit(U_JNZ, res);
+    nreg_ = res + 1;
+    emit(U_MOV, res, unchanged(sn, mask));
+    patch(j, pc());
+    emit(U_RET, res);
+  }
 
   // compiles definition `name` as user invariant k
   void compile(int k, const std::string& name) {
@@ -713,6 +759,80 @@ class Compiler {
   int nreg_ = 0;
   int depth_ = 0;
   int dry_ = 0;  // > 0: type probing (code is discarded)
+  bool action_ = false;  // x' and UNCHANGED are expressions (an action property)
+
+  // ---- the variables (compaction.tla:57-70, declaration order) and tuples of them
+  static constexpr int kNVars = 9;
+  static const char* var_name(int i) {
+    static const char* kVars[kNVars] = {"messages", "compactedLedgers", "cursor", "compactorState", "phaseOneResult",
+                                        "compactionHorizon", "compactedTopicContext", "crashTimes", "consumeTimes"};
+    return kVars[i];
+  }
+  static int var_index(const std::string& s) {
+    for (int i = 0; i < kNVars; ++i)
+      if (s == var_name(i)) return i;
+    return -1;
+  }
+  // e flattened to variables: a variable, a tuple of such, a name defined as one
+  // (the module's own vars, bookieVars, compactorVars, otherVars where the
+  // definitions do not hold them)
+  void flatten_vars(const NodeP& n, const EnvP& env, uint32_t* mask, const std::string& what, int depth = 0) {
+    if (depth > 50) fail(n, what + " nests too deeply");
+    if (n->k == Node::TUPLE) {
+      for (const NodeP& c : n->c) flatten_vars(c, env, mask, what, depth + 1);
+      return;
+    }
+    if (n->k == Node::ID) {
+      const Env* owner = nullptr;
+      if (const Bind* b = env->find(n->s, &owner)) {
+        if (b->by_name && b->params.empty()) {
+          const EnvP benv = b->own_env ? std::const_pointer_cast<Env>(owner->shared_from_this()) : b->env;
+          return flatten_vars(b->node, benv, mask, what, depth + 1);
+        }
+        fail(n, what + " must be variables, not " + n->s);
+      }
+      auto it = defs.find(n->s);
+      if (it != defs.end()) {
+        if (!it->second.params.empty()) fail(n, what + " must be variables, not the operator " + n->s);
+        return flatten_vars(body_of(it->second), std::make_shared<Env>(), mask, what, depth + 1);
+      }
+      const int v = var_index(n->s);
+      if (v >= 0) {
+        *mask |= 1u << v;
+        return;
+      }
+      static const struct { const char* name; uint32_t m; } kTuples[] = {
+          {"bookieVars", 0x7}, {"compactorVars", 0x78}, {"otherVars", 0x180}, {"vars", 0x1ff}};
+      for (const auto& t : kTuples)
+        if (n->s == t.name) {
+          *mask |= t.m;
+          return;
+        }
+      fail(n, what + " must be variables, not " + n->s);
+    }
+    fail(n, what + " must be a variable, a tuple << >> of variables or a name defined as one");
+  }
+  // the conjunction of x' = x over the variables of mask, left to right
+  int unchanged(const NodeP& at, uint32_t mask) {
+    const int r = R();
+    emit(U_LDI, r, 0, 0, 1);
+    std::vector<int> exits;
+    for (int i = 0; i < kNVars; ++i) {
+      if (!(mask >> i & 1)) continue;
+      const int mark = nreg_;
+      auto id = std::make_shared<Node>(*at);
+      id->k = Node::ID;
+      id->s = var_name(i);
+      id->c.clear();
+      const Val b = var_or_const(id, false), a = var_or_const(id, true);
+      emit(U_MOV, r, equal(at, a, b));
+      exits.push_back(emit(U_JZ, r));
+      nreg_ = mark;
+    }
+    for (int e : exits) patch(e, pc());
+    return r;
+  }
+  int state_op(int op, bool nx, int a, int b = 0, int c = 0) { return emit(op, a, b, c, nx ? 1 : 0); }
 
   int pc() const { return P_->n_ins; }
   int emit(int op, int a = 0, int b = 0, int c = 0, int imm = 0) {
@@ -745,7 +865,7 @@ class Compiler {
     if (!d.parsed) {
       d.parsed = true;
       try {
-        Parser p(lex(d.text, d.line0));
+        Parser p(lex(d.text, d.line0), action_);
         d.body = p.parse_all();
       } catch (const CompileError& e) {
         d.err = e.what();
@@ -775,17 +895,18 @@ class Compiler {
   }
 
   // ---- values of the state and the constants
-  Val var_or_const(const NodeP& n) {
+  Val var_or_const(const NodeP& n, bool nx = false) {
     const std::string& s = n->s;
     Val v;
+    v.nx = nx;
     auto reg1 = [&](int op) {
       v.r[0] = R();
-      emit(op, v.r[0]);
+      state_op(op, nx, v.r[0]);
     };
     if (s == "messages") {  // the whole sequence: positions 1..Len
       v.t = T_SEQ;
       const int len = R();
-      emit(U_LEN, len);
+      state_op(U_LEN, nx, len);
       v.r[0] = R();
       emit(U_MASK, v.r[0], len);
       return v;
@@ -797,19 +918,19 @@ class Compiler {
     if (s == "cursor") {
       v.t = T_CUR;
       const int p = R();
-      emit(U_CURP, p);
+      state_op(U_CURP, nx, p);
       v.nil = R();
       emit(U_NOT, v.nil, p);
       v.r[0] = R();
-      emit(U_CURH, v.r[0]);
+      state_op(U_CURH, nx, v.r[0]);
       v.r[1] = R();
-      emit(U_CURC, v.r[1]);
+      state_op(U_CURC, nx, v.r[1]);
       return v;
     }
     if (s == "phaseOneResult") {
       v.t = T_P1R;
       v.r[0] = R();
-      emit(U_P1R, v.r[0]);
+      state_op(U_P1R, nx, v.r[0]);
       const int z = ldi(0);
       v.nil = R();
       emit(U_EQ, v.nil, v.r[0], z);
@@ -1009,6 +1130,15 @@ class Compiler {
       case Node::APP: return apply(n, env);
       case Node::FIELD: return field(n, env);
       case Node::RECORD: return record(n, env);
+      case Node::PRIME: return primed(n, env);
+      case Node::UNCHANGED: {
+        uint32_t mask = 0;
+        flatten_vars(n->c[0], env, &mask, "the operand of UNCHANGED");
+        Val v;
+        v.t = T_BOOL;
+        v.r[0] = unchanged(n, mask);
+        return v;
+      }
       case Node::TUPLE: {
         if (!n->c.empty()) fail(n, "only the empty sequence << >> is supported as a tuple");
         Val v;
@@ -1018,6 +1148,14 @@ class Compiler {
       }
     }
     fail(n, "unsupported expression");
+  }
+
+  // x': the variable x in the successor state
+  Val primed(const NodeP& n, const EnvP& env) {
+    const NodeP& x = n->c[0];
+    if (env->find(x->s) || defs.count(x->s) || var_index(x->s) < 0)
+      fail(n, "a prime (') on " + x->s + ", which is not a variable");
+    return var_or_const(x, true);
   }
 
   // an identifier (or operator application) in scope
@@ -1105,6 +1243,8 @@ class Compiler {
   // the type of IF a THEN x ELSE y: equal types, or a composite and Nil
   Val joined(const NodeP& n, const Val& a, const Val& b) {
     auto composite = [](TK t) { return t == T_MSG || t == T_SEQ || t == T_CUR || t == T_P1R; };
+    if (a.t == b.t && a.nx != b.nx && (a.t == T_SEQ || a.t == T_P1R))
+      fail(n, "branches that mix a value of the state with one of its successor");
     if (a.t == b.t && a.t != T_SET && a.t != T_FUNC && a.t != T_LEDGERS && a.t != T_LFK) {
       Val r = alloc_like(a);
       if (r.nil < 0 && b.nil >= 0) r.nil = R();
@@ -1274,6 +1414,27 @@ class Compiler {
       for (int e : exits) patch(e, pc());
       return r;
     }
+    if (a.t == T_LEDGERS && b.t == T_LEDGERS && action_) {  // ledger by ledger: both Nil, or the same sequence
+      emit(U_LDI, r, 0, 0, 1);
+      for (int i = 1; i <= L_.C; ++i) {
+        const int mark = nreg_;
+        const int ix = ldi(i), pa = R(), pb = R(), ma = R(), mb = R(), e = R();
+        state_op(U_LEDP, a.nx, pa, ix);
+        state_op(U_LEDP, b.nx, pb, ix);
+        state_op(U_LEDM, a.nx, ma, ix);
+        state_op(U_LEDM, b.nx, mb, ix);
+        emit(U_EQ, e, pa, pb);
+        emit(U_AND, r, r, e);
+        emit(U_EQ, e, ma, mb);
+        emit(U_AND, r, r, e);
+        if (a.nx != b.nx) {
+          emit(U2_MSAME, e, ma);
+          emit(U_AND, r, r, e);
+        }
+        nreg_ = mark;
+      }
+      return r;
+    }
     const bool ca = a.t == T_MSG || a.t == T_SEQ || a.t == T_CUR || a.t == T_P1R;
     const bool cb = b.t == T_MSG || b.t == T_SEQ || b.t == T_CUR || b.t == T_P1R;
     if (ca && b.t == T_MV) return nil_equal(a, b, r);
@@ -1285,6 +1446,18 @@ class Compiler {
     if (a.t != b.t || !ca) fail(n, std::string("cannot compare a ") + tk_name(a.t) + " with a " + tk_name(b.t));
     const int k = a.t == T_MSG ? 3 : a.t == T_CUR ? 2 : 1;
     fields_equal(k);
+    if (a.nx != b.nx && (a.t == T_SEQ || a.t == T_P1R)) {
+      // one of the state, one of its successor: the messages behind the mask
+      // (behind 1..readPosition, which decide latestForKey) must agree too
+      int m = a.r[0];
+      if (a.t == T_P1R) {
+        m = R();
+        emit(U_MASK, m, a.r[0]);
+      }
+      const int e = R();
+      emit(U2_MSAME, e, m);
+      emit(U_AND, r, r, e);
+    }
     if (a.nil >= 0 || b.nil >= 0) {  // equal iff both Nil, or neither and the fields agree
       const int na = a.nil >= 0 ? a.nil : ldi(0), nb = b.nil >= 0 ? b.nil : ldi(0);
       const int both = R(), same = R(), none = R();
@@ -1340,6 +1513,7 @@ class Compiler {
       }
       v.t = T_LFK;
       v.r[0] = r.r[0];
+      v.nx = r.nx;
       return v;
     }
     if (r.t == T_MV) {  // e.g. Nil.f: always an evaluation error when reached
@@ -1394,9 +1568,9 @@ class Compiler {
     m.r[0] = R();
     emit(U_NTH, m.r[0], s.r[0], j);  // the id is the message's position
     m.r[1] = R();
-    emit(U_MKEY, m.r[1], m.r[0]);
+    state_op(U_MKEY, s.nx, m.r[1], m.r[0]);
     m.r[2] = R();
-    emit(U_MVAL, m.r[2], m.r[0]);
+    state_op(U_MVAL, s.nx, m.r[2], m.r[0]);
     return m;
   }
 
@@ -1413,18 +1587,19 @@ class Compiler {
       Val s;
       s.t = T_SEQ;
       const int p = R();
-      emit(U_LEDP, p, i);
+      s.nx = f.nx;
+      state_op(U_LEDP, f.nx, p, i);
       s.nil = R();
       emit(U_NOT, s.nil, p);
       s.r[0] = R();
-      emit(U_LEDM, s.r[0], i);
+      state_op(U_LEDM, f.nx, s.r[0], i);
       return s;
     }
     if (f.t == T_LFK) {  // latestForKey[k]: k in GetKeys(messages[1..readPosition]) \ {NullKey}
       const int k = integer(n->c[1], env);
       Val v;
       v.r[0] = R();
-      emit(U_LFK, v.r[0], k, f.r[0]);
+      state_op(U_LFK, f.nx, v.r[0], k, f.r[0]);
       const int z = ldi(0), ok = R(), nz = R();
       emit(U_NE, ok, v.r[0], z);
       emit(U_NE, nz, k, z);
@@ -1664,15 +1839,15 @@ class Compiler {
         const int j = emit(U_JZ, c);
         Val x;
         x.r[0] = R();
-        emit(U_MKEY, x.r[0], p);
+        state_op(U_MKEY, f.nx, x.r[0], p);
         const int isz = R();
         emit(U_EQ, isz, x.r[0], z);
         const int skip0 = emit(U_JNZ, isz);
         const int last = R();  // latest position of this key up to r: the key is first seen at p iff ...
-        emit(U_LFK, last, x.r[0], p);  // ... the latest position within 1..p is p and none before
+        state_op(U_LFK, f.nx, last, x.r[0], p);  // ... the latest position within 1..p is p and none before
         const int q = R(), prev = R();
         emit(U_ADDI, q, p, 0, -1);
-        emit(U_LFK, prev, x.r[0], q);
+        state_op(U_LFK, f.nx, prev, x.r[0], q);
         const int seen = R();
         emit(U_NE, seen, prev, z);
         const int skip1 = emit(U_JNZ, seen);
@@ -2322,6 +2497,89 @@ int compile_property(const tlcg_model& m, const HostModel& hm, const std::string
     *err = "property " + name + " cannot be checked: " + e.what();
     return -1;
   } catch (const std::exception& e) {  // (a numeral past 64 bits: std::stoll)
+    *err = "property " + name + " cannot be checked: " + e.what();
+    return -1;
+  }
+  return 0;
+}
+
+// ---------------------------------------------------------------- action properties
+// [][A]_v: a definition whose body, outer parentheses stripped, is the tokens
+// [] [ A ] and a subscript _name or _<<...>>, nothing after it.  A is an
+// expression of the subset with x' for a variable x and UNCHANGED e; the
+// program compiled (entry 0) is A \/ UNCHANGED v, A first.
+int compile_action_property(const tlcg_model& m, const HostModel& hm, const std::string& name, uint32_t* var_mask,
+                            UserProg* P, std::string* err) {
+  std::vector<Def> defs = split_defs(m.user_defs ? m.user_defs : "");
+  Def* d = nullptr;
+  for (Def& x : defs)
+    if (x.name == name) d = &x;
+  if (!d) {
+    *err = "property " + name + " is not defined";
+    return -3;
+  }
+  try {
+    const std::vector<Tok> toks = lex(d->text, d->line0);
+    const PropScan s(toks);
+    size_t lo = 0, hi = toks.size() - 1;
+    if (hi == 0) {
+      *err = "property " + name + " is not of the form [][A]_v";
+      return -2;
+    }
+    s.strip(&lo, &hi);
+    auto subscripted = [&](size_t open) {  // <<...>>_v or [...]_v: an identifier _... right behind the closer
+      const long c = s.mate[open];
+      return c >= 0 && (size_t)c + 1 < hi && toks[(size_t)c + 1].k == Tok::ID && toks[(size_t)c + 1].s[0] == '_' &&
+             toks[(size_t)c + 1].off == toks[(size_t)c].end;
+    };
+    const size_t br = s.op(lo, "[]") ? lo + 1 : lo;
+    if (s.op(br, "<<") && subscripted(br))
+      s.refuse(br, "<<A>>_v (an action that must change v; only [][A]_v is implemented)");
+    if (!(s.op(lo, "[]") && s.op(lo + 1, "["))) {
+      *err = "property " + name + " is not of the form [][A]_v";
+      return -2;
+    }
+    if (!d->params.empty()) throw CompileError("it takes arguments");
+    const long close = s.mate[lo + 1];
+    if (close < 0 || (size_t)close >= hi) s.refuse(lo + 1, "[][ without its closing ]");
+    const size_t sub = (size_t)close + 1;
+    if (sub >= hi || toks[sub].k != Tok::ID || toks[sub].s[0] != '_')
+      s.refuse(std::min(sub, hi - 1), "[][A] without a subscript _v");
+    if ((size_t)close == lo + 2) s.refuse(lo + 1, "[][ ]_v without an action");
+    Def act, subd;
+    act.name = subd.name = name;
+    act.line0 = subd.line0 = d->line0;
+    act.text = blank_outside(d->text, toks, lo + 2, (size_t)close);
+    size_t after;
+    if (toks[sub].s.size() > 1) {  // _name
+      subd.text = d->text;
+      for (char& ch : subd.text)
+        if (ch != '\n') ch = ' ';
+      subd.text.replace(toks[sub].off + 1, toks[sub].s.size() - 1, toks[sub].s.substr(1));
+      after = sub + 1;
+    } else {  // _<<...>>
+      if (!(s.op(sub + 1, "<<") && s.mate[sub + 1] >= 0 && (size_t)s.mate[sub + 1] < hi))
+        s.refuse(std::min(sub + 1, hi - 1), "a subscript that is not a variable, a tuple << >> of variables or a "
+                                            "name defined as one");
+      after = (size_t)s.mate[sub + 1] + 1;
+      subd.text = blank_outside(d->text, toks, sub + 1, after);
+    }
+    if (after < hi) s.refuse(after, "text after the subscript of [][A]_v ('" + toks[after].s + "'; conjunctions of "
+                                    "temporal formulas are not implemented)");
+    std::unique_ptr<UserProg> scratch;
+    if (!P) {
+      scratch.reset(new UserProg);
+      P = scratch.get();
+    }
+    if (!prog_tables(hm, P, err)) return -3;
+    Compiler c(hm, P, true);
+    for (Def& x : defs) c.defs[x.name] = x;
+    P->n_user = 1;
+    c.compile_action(0, act, subd, "property " + name, " at " + where(toks[lo + 2].line, toks[lo + 2].col), var_mask);
+  } catch (const CompileError& e) {
+    *err = "property " + name + " cannot be checked: " + e.what();
+    return -1;
+  } catch (const std::exception& e) {
     *err = "property " + name + " cannot be checked: " + e.what();
     return -1;
   }

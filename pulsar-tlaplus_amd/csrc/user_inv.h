@@ -66,6 +66,15 @@ enum UOp : uint8_t {
   U_ERR,     // evaluation error
   U_RET,     // return r[a] ? TRUE : FALSE
 };
+// Two-state programs (an action property's A \/ UNCHANGED v,
+// compile_action_property): a state-reading op (U_LEN .. U_LFK) with imm = 1
+// reads the successor state of the step (x'), and one op more compares the
+// two states.  Only the two-view interpreter eval_user2_v runs such programs;
+// the one-view interpreter, the generated device code and the read analysis
+// never see one.
+enum UOp2 : uint8_t {
+  U2_MSAME = 64,  // r[a] = messages[p] is the same message in both states, for every bit p-1 of r[b]
+};
 
 struct UInsn {
   uint8_t op, a, b, c;
@@ -174,10 +183,108 @@ TLCG_HD int eval_user_v(const UserProg& P, int k, const V& v) {
   }
 }
 
+// Runs entry k of a two-state program on the step v -> vn (the views of the
+// state and of its successor): EV_TRUE / EV_FALSE / EV_ERROR.  The one-state
+// interpreter above with the state-reading ops choosing their view by imm.
+template <class V>
+TLCG_HD int eval_user2_v(const UserProg& P, int k, const V& v, const V& vn) {
+  long long r[UI_MAXREG];
+  int pc = P.entry[k];
+  int loops = 0;
+  for (;;) {
+    const int at = pc;
+    const UInsn in = P.ins[pc++];
+    const V& w = in.op >= U_LEN && in.op <= U_LFK && in.imm ? vn : v;
+    switch (in.op) {
+      case U_LDI: r[in.a] = in.imm; break;
+      case U_MOV: r[in.a] = r[in.b]; break;
+      case U_LEN: r[in.a] = w.len(); break;
+      case U_MKEY: r[in.a] = P.keyval[w.key((int)r[in.b]) & (UI_MAXSET - 1)]; break;
+      case U_MVAL: r[in.a] = P.valval[w.val((int)r[in.b]) & (UI_MAXSET - 1)]; break;
+      case U_PHASE: r[in.a] = UV_PHASE0 + w.phase(); break;
+      case U_P1R: r[in.a] = w.p1r(); break;
+      case U_HZ: r[in.a] = w.hz(); break;
+      case U_CTX: r[in.a] = w.ctx(); break;
+      case U_CRASH: r[in.a] = w.crash(); break;
+      case U_CURP: r[in.a] = w.curp(); break;
+      case U_CURH: r[in.a] = w.curh(); break;
+      case U_CURC: r[in.a] = w.curc(); break;
+      case U_LEDP: r[in.a] = w.ledp((int)r[in.b]); break;
+      case U_LEDM: r[in.a] = (long long)w.ledm((int)r[in.b]); break;
+      case U_LFK: {
+        long long best = 0;
+        for (int i = 1; i <= (int)r[in.c] && i <= w.L.N; ++i)
+          if (P.keyval[w.key(i) & (UI_MAXSET - 1)] == r[in.b]) best = i;
+        r[in.a] = best;
+        break;
+      }
+      case U_ADD: r[in.a] = r[in.b] + r[in.c]; if (ui_overflows(r[in.a])) return EV_ERROR; break;
+      case U_SUB: r[in.a] = r[in.b] - r[in.c]; if (ui_overflows(r[in.a])) return EV_ERROR; break;
+      case U_MUL: r[in.a] = r[in.b] * r[in.c]; if (ui_overflows(r[in.a])) return EV_ERROR; break;
+      case U_DIV: {
+        const long long q = r[in.b] / r[in.c];
+        r[in.a] = (r[in.b] % r[in.c] != 0 && ((r[in.b] < 0) != (r[in.c] < 0))) ? q - 1 : q;
+        break;
+      }
+      case U_MOD: {
+        const long long m = r[in.b] % r[in.c];
+        r[in.a] = m < 0 ? m + r[in.c] : m;
+        break;
+      }
+      case U_NEG: r[in.a] = -r[in.b]; if (ui_overflows(r[in.a])) return EV_ERROR; break;
+      case U_EQ: r[in.a] = r[in.b] == r[in.c]; break;
+      case U_NE: r[in.a] = r[in.b] != r[in.c]; break;
+      case U_LT: r[in.a] = r[in.b] < r[in.c]; break;
+      case U_LE: r[in.a] = r[in.b] <= r[in.c]; break;
+      case U_NOT: r[in.a] = !r[in.b]; break;
+      case U_AND: r[in.a] = r[in.b] & r[in.c]; break;
+      case U_OR: r[in.a] = r[in.b] | r[in.c]; break;
+      case U_ADDI: r[in.a] = r[in.b] + in.imm; break;
+      case U_BIT: r[in.a] = (r[in.c] >= 1 && r[in.c] <= 63) ? (r[in.b] >> (r[in.c] - 1)) & 1 : 0; break;
+      case U_POPC: r[in.a] = popcount64((u64)r[in.b]); break;
+      case U_NTH: r[in.a] = ui_nth((u64)r[in.b], r[in.c]); break;
+      case U_MASK: r[in.a] = (long long)((1ull << (r[in.b] & 63)) - 1); break;
+      case U_KIN: {
+        const int n = in.imm ? P.nv : P.nk;
+        const int32_t* t = in.imm ? P.valsorted : P.keysorted;
+        long long f = 0;
+        for (int i = 0; i < n && i < UI_MAXSET; ++i) f |= t[i] == r[in.b];
+        r[in.a] = f;
+        break;
+      }
+      case U_KAT: {
+        const int i = (int)r[in.b] & (UI_MAXSET - 1);
+        r[in.a] = in.imm ? P.valsorted[i] : P.keysorted[i];
+        break;
+      }
+      case U_JMP: pc = in.imm; break;
+      case U_JZ: if (!r[in.a]) pc = in.imm; break;
+      case U_JNZ: if (r[in.a]) pc = in.imm; break;
+      case U_ERR: return EV_ERROR;
+      case U_RET: return r[in.a] ? EV_TRUE : EV_FALSE;
+      case U2_MSAME: {
+        long long same = 1;
+        for (int i = 1; i <= v.L.N && i <= 63; ++i)
+          if (((u64)r[in.b] >> (i - 1)) & 1) same &= v.key(i) == vn.key(i) && v.val(i) == vn.val(i);
+        r[in.a] = same;
+        break;
+      }
+      default: return EV_ERROR;
+    }
+    if (pc <= at && ++loops > UI_MAXLOOP) return EV_ERROR;  // a taken backward jump
+  }
+}
+
 // Runs user invariant k on state s: EV_TRUE / EV_FALSE / EV_ERROR.
 template <typename W>
 TLCG_HD int eval_user(const Layout& L, const UserProg& P, int k, W s) {
   return eval_user_v(P, k, UVWord<W>{L, s});
+}
+
+// Runs entry k on the step s -> t.
+template <typename W>
+TLCG_HD int eval_user2(const Layout& L, const UserProg& P, int k, W s, W t) {
+  return eval_user2_v(P, k, UVWord<W>{L, s}, UVWord<W>{L, t});
 }
 
 // Every invariant of the cfg in its order -- the spec's own (model.h) and the

@@ -642,7 +642,18 @@ bool bind_model(const Config& cfg, const Module& mod, bool deadlock_flag, tlcg_m
     int32_t form = 0;
     char e[1024] = {0};
     // (a model that does not build is reported by tlcg_check_model, with its own message)
-    const int rc = tlcg_check_model(m, nullptr, 0) == 0 ? tlcg_host_property_form(m, name.c_str(), &form, e, sizeof e) : 0;
+    const bool model_ok = tlcg_check_model(m, nullptr, 0) == 0;
+    // an action property [][A]_v goes to the action front end; -2 (the body
+    // does not start with [][) and -3 go on to the temporal one unchanged
+    const int arc = model_ok ? tlcg_host_action_property_form(m, name.c_str(), nullptr, e, sizeof e) : -2;
+    if (arc == 0) continue;
+    if (arc == -1) {
+      *err = std::string("Error: ") + e;
+      *exit_code = 150;
+      return false;
+    }
+    e[0] = 0;
+    const int rc = model_ok ? tlcg_host_property_form(m, name.c_str(), &form, e, sizeof e) : 0;
     if (rc == -1) {
       *err = std::string("Error: ") + e;
       *exit_code = 150;  // as a user invariant outside the subset

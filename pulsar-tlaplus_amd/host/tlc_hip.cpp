@@ -316,7 +316,7 @@ int main(int argc, char** argv) {
   // complete state space ([TLC-ext] message text), on the GPU
   // (tlcg_check_termination: the not-P part of the state graph, its stuck
   // states and, under fairness, its cycles)
-  bool live_fail = false;
+  bool live_fail = false, action_fail = false;
   std::string violated;  // the property the counterexample above is of
   if (st.status == TLCG_DONE && !cfg.properties.empty()) {
     std::printf("Checking temporal properties for the complete state space with %llu total distinct states at (%s)\n",
@@ -334,10 +334,54 @@ int main(int argc, char** argv) {
     // defined; it halves the capacity until they fit and grows it x4 only if
     // the graph needs more, liveness.hip)
     double live_ms = 0;
-    // the cfg's properties in order, up to the first one violated: Termination
+    // Action properties [][A]_v first (tlcg_check_action_property: every step
+    // of the reachable graph), in the cfg's order up to the first one violated.
+    // [TLC-ext] TLC checks them inside its BFS and stops at the first error it
+    // meets, an invariant's or a step's; here the safety search has completed
+    // (an invariant violation wins and ends the run before this point), and
+    // the counts printed are the completed search's.
+    std::vector<std::string> temporal;
+    for (const std::string& pname : cfg.properties) {
+      if (action_fail || property_is_published_termination(mod, pname) ||
+          tlcg_host_action_property_form(&model, pname.c_str(), nullptr, nullptr, 0) != 0) {
+        temporal.push_back(pname);
+        continue;
+      }
+      int32_t ln = 0;
+      char lerr[1024] = {0};
+      tlcg_action_property ap;
+      const int arc = tlcg_check_action_property(&model, &lo, pname.c_str(), &ap, lstates.data(), lacts.data(),
+                                                 (int32_t)lacts.size(), &ln, lerr, (int32_t)sizeof lerr);
+      if (arc != 0 && arc != -7) {
+        std::printf("Error: the action property check failed: %s\n", lerr);
+        std::printf("Finished in %s at (%s)\n", duration_str(0).c_str(), now_str().c_str());
+        return 255;
+      }
+      live_ms += ap.wall_ms;
+      if (arc == 0 && ap.holds) continue;
+      std::vector<char> buf(1 << 16);
+      if (arc == -7) std::printf("Error: Evaluating property %s failed: %s.\n", pname.c_str(), lerr);
+      else std::printf("Error: Action property %s is violated.\n", pname.c_str());
+      std::printf("Error: The behavior up to this point is:\n");
+      for (int i = 0; i < ln; ++i) {  // (the last state is the step's successor)
+        if (lacts[(size_t)i] < 0) std::printf("State %d: <Initial predicate>\n", i + 1);
+        else std::printf("State %d: <%s>\n", i + 1, action_location(mod, lacts[(size_t)i]).c_str());
+        tlcg_decode_words(&model, &lstates[(size_t)i * words], buf.data(), (int32_t)buf.size());
+        std::printf("%s\n\n", buf.data());
+      }
+      if (arc == -7) {
+        std::printf("Finished in %s at (%s)\n", duration_str(0).c_str(), now_str().c_str());
+        tlcg_destroy(ctx);
+        return 75;
+      }
+      action_fail = true;
+      violated = pname;
+    }
+    // then the temporal ones, up to the first one violated: Termination
     // as published by tlcg_check_termination, a property the user defined
     // (<>Q, []<>Q, P ~> Q) by tlcg_check_property
-    for (const std::string& pname : cfg.properties) {
+    if (action_fail) temporal.clear();
+    for (const std::string& pname : temporal) {
       int32_t ln = 0;
       tlcg_liveness lv;
       char lerr[1024] = {0};
@@ -395,7 +439,9 @@ int main(int argc, char** argv) {
       std::printf("Finished checking temporal properties in %s at %s\n", duration_str(live_ms / 1000.0).c_str(),
                   now_str().c_str());
   }
-  if (live_fail) {
+  if (action_fail) {
+    rc = 12;  // TLC's safety-violation status
+  } else if (live_fail) {
     rc = 13;
   } else if (st.status == TLCG_DONE) {
     std::printf("Model checking completed. No error has been found.\n");

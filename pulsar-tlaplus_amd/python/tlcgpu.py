@@ -72,6 +72,17 @@ class tlcg_property(C.Structure):
                 ("seeds", C.c_uint64), ("error_state", C.c_int64), ("classify_ms", C.c_double)]
 
 
+class tlcg_action_property(C.Structure):
+    _fields_ = [("holds", C.c_int32), ("depth", C.c_int32), ("reachable", C.c_uint64), ("steps", C.c_uint64),
+                ("violating", C.c_uint64), ("erroring", C.c_uint64), ("step_depth", C.c_int32),
+                ("step_action", C.c_int32), ("trace_len", C.c_int32), ("reserved", C.c_int32),
+                ("error_state", C.c_int64), ("kernel_ms", C.c_double), ("check_ms", C.c_double),
+                ("wall_ms", C.c_double)]
+
+
+# compaction.tla:57-70, declaration order: the bits of host_action_property_form's mask
+VARIABLES = ("messages", "compactedLedgers", "cursor", "compactorState", "phaseOneResult", "compactionHorizon",
+             "compactedTopicContext", "crashTimes", "consumeTimes")
 FAIRNESS = {"none": 0, "wf": 1}
 PROP_FORMS = {0: "eventually", 1: "infinitely_often", 2: "leads_to"}
 PROP_FORM_IDS = {v: k for k, v in PROP_FORMS.items()}
@@ -173,6 +184,16 @@ def load_library(path: str = LIB_PATH):
                                                    I32]),
         "tlcg_host_property_form": (C.c_int, [M, C.c_char_p, C.POINTER(I32), C.c_char_p, I32]),
         "tlcg_host_property_eval": (C.c_int, [M, C.c_char_p, C.POINTER(U64), U64, C.POINTER(C.c_uint8)]),
+        "tlcg_check_action_property": (C.c_int, [M, O, C.c_char_p, C.POINTER(tlcg_action_property), C.POINTER(U64),
+                                                 C.POINTER(I32), I32, C.POINTER(I32), C.c_char_p, I32]),
+        "tlcg_action_property_graph_selftest": (C.c_int, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                                          C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32, I32, O,
+                                                          C.POINTER(tlcg_action_property), C.POINTER(U64),
+                                                          C.POINTER(I32), I32, C.POINTER(I32), C.c_char_p, I32]),
+        "tlcg_host_action_property_form": (C.c_int, [M, C.c_char_p, C.POINTER(C.c_uint32), C.c_char_p, I32]),
+        "tlcg_host_action_property_eval": (C.c_int, [M, C.c_char_p, C.POINTER(U64), U64, C.POINTER(C.c_uint8)]),
+        "tlcg_action_eval_selftest": (C.c_int, [M, O, C.c_char_p, C.POINTER(U64), U64, C.POINTER(C.c_uint8),
+                                                C.c_char_p, I32]),
         "tlcg_jit_selftest": (C.c_int, [M, C.c_char_p, I32, C.c_char_p, I32][:1] + [C.c_char_p, C.c_char_p, I32]),
         "tlcg_user_eval_selftest": (C.c_int, [M, O, C.POINTER(U64), U64, I32, C.POINTER(C.c_uint8), C.c_char_p, I32]),
     }
@@ -605,6 +626,144 @@ def property_graph(row: Sequence[int], col: Sequence[int], is_p: Sequence[int], 
         raise RuntimeError(f"tlcg_property_graph_selftest: {rc}: {err.value.decode()}")
     trace = [("Init" if acts[i] < 0 else acts[i], _from_words(states, i, words)) for i in range(ln.value)]
     return _property_of(out, fairness, trace, out.lv.back_action)
+
+
+@dataclass
+class ActionProperty:
+    """A user-defined [][A]_v checked on the GPU (tlcg_check_action_property)."""
+    holds: bool
+    kind: str                    # "holds", "violated" or "error"
+    depth: int                   # levels of the reachable graph
+    reachable: int
+    steps: int                   # steps evaluated (successors that differ from their state)
+    violating: int
+    erroring: int
+    step_depth: int              # level of the reported step's source
+    step_action: Optional[object]  # its action (a name; an edge ordinal on an explicit graph), None when it holds
+    trace: List[Tuple[object, int]] = field(default_factory=list)  # (action into it, state); the last one is t
+    error_state: int = -1
+    error: Optional[str] = None
+    kernel_ms: float = 0.0
+    check_ms: float = 0.0
+    wall_ms: float = 0.0
+
+
+def _pairs_buf(model: "Model", pairs: Sequence[Tuple[int, int]]):
+    w = state_words(model)
+    buf = (C.c_uint64 * max(1, 2 * len(pairs) * w))()
+    for i, (s, t) in enumerate(pairs):
+        for k in range(w):
+            buf[2 * i * w + k] = (s >> (64 * k)) & 0xFFFFFFFFFFFFFFFF
+            buf[(2 * i + 1) * w + k] = (t >> (64 * k)) & 0xFFFFFFFFFFFFFFFF
+    return buf
+
+
+def host_action_property_form(model: Model, name: str) -> Tuple[str, ...]:
+    """The front end alone on action property `name` ([][A]_v, a definition of
+    model.user_defs): the subscript's variables, flattened, in declaration order.
+    ValueError with the front end's message when it is refused; LookupError
+    when the definition is not an action property at all (rc -2) or is missing."""
+    m = model.to_c()
+    mask = C.c_uint32(0)
+    err = C.create_string_buffer(1024)
+    rc = load_library().tlcg_host_action_property_form(C.byref(m), name.encode(), C.byref(mask), err, len(err))
+    if rc == -1:
+        raise ValueError(err.value.decode())
+    if rc != 0:
+        raise LookupError(f"{rc}: {err.value.decode()}")
+    return tuple(v for i, v in enumerate(VARIABLES) if mask.value >> i & 1)
+
+
+def host_action_property_eval(model: Model, name: str, pairs: Sequence[Tuple[int, int]]) -> List[int]:
+    """A \\/ UNCHANGED v of action property `name` on every step (s, t), by the
+    host interpreter: 0 TRUE, 1 FALSE, 2 an evaluation error"""
+    m = model.to_c()
+    out = (C.c_uint8 * max(1, len(pairs)))()
+    rc = load_library().tlcg_host_action_property_eval(C.byref(m), name.encode(), _pairs_buf(model, pairs),
+                                                       len(pairs), out)
+    if rc != 0:
+        raise ValueError(f"tlcg_host_action_property_eval: {rc}")
+    return list(out)[:len(pairs)]
+
+
+def action_eval_device(model: Model, name: str, pairs: Sequence[Tuple[int, int]], device: int = 0) -> List[int]:
+    """The same on the device (tlcg_action_eval_selftest), one lane per step"""
+    m = model.to_c()
+    o = tlcg_opts()
+    o.device = device
+    out = (C.c_uint8 * max(1, len(pairs)))()
+    err = C.create_string_buffer(1024)
+    rc = load_library().tlcg_action_eval_selftest(C.byref(m), C.byref(o), name.encode(), _pairs_buf(model, pairs),
+                                                  len(pairs), out, err, len(err))
+    if rc == -2:
+        raise ValueError(err.value.decode())
+    if rc != 0:
+        raise RuntimeError(f"tlcg_action_eval_selftest: {rc}: {err.value.decode()}")
+    return list(out)[:len(pairs)]
+
+
+def _action_property_of(out, trace, act, error=None) -> ActionProperty:
+    kind = "error" if out.error_state >= 0 else "holds" if out.holds else "violated"
+    return ActionProperty(bool(out.holds), kind, out.depth, out.reachable, out.steps, out.violating, out.erroring,
+                          out.step_depth, act, trace, out.error_state, error, out.kernel_ms, out.check_ms, out.wall_ms)
+
+
+def check_action_property(model: Model, name: str, device: int = 0, state_capacity: int = 0,
+                          log2_fpset_slots: int = 0) -> ActionProperty:
+    """A safety property over steps, [][A]_v (a definition of model.user_defs),
+    checked on every step of the reachable graph through
+    tlcg_check_action_property.  A refused property is a ValueError; an
+    evaluation error of A on the reported step comes back as kind "error" with
+    error_state, the message and the trace ending in that step."""
+    lib = load_library()
+    m = model.to_c()
+    o = tlcg_opts()
+    o.device, o.state_capacity, o.log2_fpset_slots = device, state_capacity, log2_fpset_slots
+    out = tlcg_action_property()
+    w = state_words(model)
+    cap = 1 << 12
+    states = (C.c_uint64 * (cap * w))()
+    acts = (C.c_int32 * cap)()
+    n = C.c_int32(0)
+    err = C.create_string_buffer(1024)
+    rc = lib.tlcg_check_action_property(C.byref(m), C.byref(o), name.encode(), C.byref(out), states, acts, cap,
+                                        C.byref(n), err, len(err))
+    if rc == -2:
+        raise ValueError(err.value.decode())
+    if rc != 0 and rc != -7:
+        raise RuntimeError(f"tlcg_check_action_property: {rc}: {err.value.decode()}")
+    trace = [("Init" if acts[i] < 0 else ACTIONS[acts[i]], _from_words(states, i, w)) for i in range(n.value)]
+    act = ACTIONS[out.step_action] if out.step_action >= 0 else None
+    return _action_property_of(out, trace, act, err.value.decode() if rc == -7 else None)
+
+
+def action_property_graph(row: Sequence[int], col: Sequence[int], verdict: Sequence[int], n_init: int,
+                          words: int = 1, device: int = 0, state_capacity: int = 0,
+                          log2_fpset_slots: int = 0) -> ActionProperty:
+    """The step pass on an explicit CSR graph (tlcg_action_property_graph_selftest):
+    row[n + 1], col[], verdict[len(col)] (0 holds, 1 violates, 2 errs), nodes
+    0 .. n_init - 1 initial.  The trace holds (edge ordinal or "Init", word)."""
+    lib = load_library()
+    n = len(row) - 1
+    if n < 0 or len(col) != row[n] or len(verdict) != len(col):
+        raise ValueError("row must hold n + 1 offsets, the last one len(col); verdict a byte per edge")
+    c_row = (C.c_uint32 * (n + 1))(*row)
+    c_col = (C.c_uint32 * max(1, len(col)))(*col)
+    c_v = (C.c_uint8 * max(1, len(col)))(*verdict)
+    o = tlcg_opts()
+    o.device, o.state_capacity, o.log2_fpset_slots = device, state_capacity, log2_fpset_slots
+    out = tlcg_action_property()
+    cap = n + 3
+    states = (C.c_uint64 * (cap * words))()
+    acts = (C.c_int32 * cap)()
+    ln = C.c_int32(0)
+    err = C.create_string_buffer(512)
+    rc = lib.tlcg_action_property_graph_selftest(c_row, c_col, c_v, n, n_init, words, C.byref(o), C.byref(out),
+                                                 states, acts, cap, C.byref(ln), err, len(err))
+    if rc != 0:
+        raise RuntimeError(f"tlcg_action_property_graph_selftest: {rc}: {err.value.decode()}")
+    trace = [("Init" if acts[i] < 0 else acts[i], _from_words(states, i, words)) for i in range(ln.value)]
+    return _action_property_of(out, trace, out.step_action if out.step_action >= 0 else None)
 
 
 @dataclass
