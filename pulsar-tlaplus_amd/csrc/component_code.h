@@ -479,6 +479,8 @@ TLCG_HD int selfloop_count_tab(const Layout& L, int term_consts, uint32_t term) 
   return (L.consumer ? 1 : 0) + (int)(term & (uint32_t)term_consts);
 }
 
+// BrokerCrash's guard alone, compaction.tla:170 (crashTimes < MaxCrashTimes)
+TLCG_HD bool crash_enabled_c(const Layout& L, ckey c) { return (int)cget(c, cc_cr(L), L.cr_w) < L.K; }
 // BrokerCrash, compaction.tla:169-182.  Returns 1 if enabled.
 TLCG_HD int crash_step_c(const Layout& L, ckey c, ckey* t) {
   const uint32_t cr = cget(c, cc_cr(L), L.cr_w);

@@ -56,6 +56,19 @@
 //     LDS read, an insert none.  FPSet.put stays exact: c is in the set iff
 //     the low half of owner[slot(c)] is c + 1 and the lane's bit of that
 //     entry's dense index is set.
+//   - round 9: without a Producer the code transitions read nothing of
+//     `messages` but its length, so the components of a cfg run in lockstep:
+//     in a given iteration BrokerCrash (crashTimes < MaxCrashTimes) is enabled
+//     in every live lane of a wave or in none, on G9 in 20 of a component's
+//     62 expansions.  Each lane still evaluates the guard on its own state;
+//     one ballot then picks one of two straight-line forms of the expansion
+//     (`expand`, TLCG_LANE_CRASH_SKIP): with the second successor, which is
+//     the kernel as it was and serves a lane without one as before, or
+//     without it (no crash_step_c, no second probe, insert, ring write or
+//     record).  The forms leave a few masks for the rare branch, which stays
+//     one copy after they join (a copy in each form spilled), and the first
+//     event of a batch goes to the result at the batch's end instead of
+//     riding in two registers across every batch.
 // LDS per 64-lane workgroup: the ring R x 256 B (the host picks R per layout,
 // jit.cpp / host_model.cpp lane_ring_entries: 8 entries, 2 KB, on G9; a wider
 // frontier sends the component to the cascade), owner 2 KB, the step table
@@ -113,6 +126,18 @@ constexpr int LANE_R = TLCG_LANE_R;  // FIFO ring entries per lane (a power of 2
 #ifndef TLCG_LANE_LEVEL_LDS
 #define TLCG_LANE_LEVEL_LDS 1
 #endif
+// round 9: the BrokerCrash successor's code (crash_step_c, its probe, insert,
+// ring write and record) only in the iterations where some live lane of the
+// wave has BrokerCrash enabled; 0: in every iteration (A/B)
+#ifndef TLCG_LANE_CRASH_SKIP
+#define TLCG_LANE_CRASH_SKIP 1
+#endif
+
+// which form of the expansion component_lane_body's `expand` compiles
+template <bool B>
+struct lane_with2 {
+  static constexpr bool value = B;
+};
 
 // the sum over the wave of x (every lane active), in a scalar
 __device__ __forceinline__ uint32_t lane_wave_sum(uint32_t x) {
@@ -167,7 +192,6 @@ __device__ __forceinline__ void component_lane_body(const CompArgs& a, const Lay
 #endif
   if (lane < LVS) lvl_sh[lane] = 0;
   uint32_t gen = 0, dist = 0, nexp = 0;  // (nexp: states expanded by the components that finish here)
-  unsigned long long ev = NO_EVENT;
   __syncthreads();
   // a level's per-lane counts (x: distinct | generated << 16) into lvl_sh: one
   // LDS add per adding lane (round 8: at 20 level ends per 62 iterations the
@@ -264,19 +288,29 @@ __device__ __forceinline__ void component_lane_body(const CompArgs& a, const Lay
 #endif
     while (__ballot(alive)) {
       const int tail0 = tail;
-      ckey t = 0, t2 = 0;
-      int action = 0;
 #if TLCG_LANE_OWNER_RING
       // (a finished lane goes on with whatever its ring holds: the index is
       // kept inside the table, every slot is below T)
       const ckey s = (cur & 0xFFFFu) - 1u;
-      const uint32_t nxt = ring[(head + 1) & (R - 1)][lane];
+      uint32_t nxt = 0, first_new = 0;
+#else
+      const ckey s = cur;
+      ckey nxt = 0, first_new = 0;
+#endif
+      // what the rare branch reads of an expansion: a deadlock, each inserted
+      // successor's invariants not known to hold (u1, u2) and how far they are
+      // decided (q1, q2: first failing + 1, or INV_UNKNOWN + 1)
+      bool out = false, rare = false, dl = false, u1 = false, u2 = false;
+      int q1 = INV_UNKNOWN + 1, q2 = INV_UNKNOWN + 1;
+      ckey t = 0;
+      int action = 0;
+#if TLCG_LANE_OWNER_RING
+      nxt = ring[(head + 1) & (R - 1)][lane];
       const uint32_t six = (cur >> LANE_OWNER_STEP_SH) & (uint32_t)(STEP_TAB - 1);
       uint32_t term = 0;
       const int r = compactor_step_ent(L, ccon, steps[six], six & 7u, s, &t, &action, &term);  // compaction.tla:221-226
 #else
-      const ckey s = cur;
-      const ckey nxt = ring[(head + 1) & (R - 1)][lane];
+      nxt = ring[(head + 1) & (R - 1)][lane];
 #if TLCG_LANE_STEP_TAB
       uint32_t term = 0;
       const int r = compactor_step_tab(L, ccon, steps, s, &t, &action, &term);  // compaction.tla:221-226
@@ -284,95 +318,124 @@ __device__ __forceinline__ void component_lane_body(const CompArgs& a, const Lay
       const int r = compactor_step_cb(L, ccon, s, &t, &action);
 #endif
 #endif
-      const bool crash = crash_step_c(L, s, &t2) != 0;            // :227
-      // FPSet.put of both successors: slot, the shared owner, the lane's bits
-      const unsigned p1 = lane_slot(t, mult), p2 = lane_slot(t2, mult);
+      // one expansion, straight-line.  W2: with the BrokerCrash successor;
+      // without it nothing of the second probe is left (no t2, no owner[p2]
+      // read, no second insert, ring write or record store)
+      auto expand = [&](auto with2) __attribute__((always_inline)) {
+        constexpr bool W2 = decltype(with2)::value;
+        ckey t2 = 0;
+        bool crash = false;
+        if constexpr (W2) crash = crash_step_c(L, s, &t2) != 0;     // :227
+        // FPSet.put of both successors: slot, the shared owner, the lane's bits
+        const unsigned p1 = lane_slot(t, mult), p2 = W2 ? lane_slot(t2, mult) : 0u;
 #if TLCG_LANE_FP_REG
-      const u64 oe1 = owner[p1], oe2 = owner[p2];
-      const uint32_t o1 = (uint32_t)oe1, o2 = (uint32_t)oe2;
+        const u64 oe1 = owner[p1], oe2 = W2 ? owner[p2] : 0ull;
+        const uint32_t o1 = (uint32_t)oe1, o2 = (uint32_t)oe2;
 #else
-      const uint32_t o1 = owner[p1], o2 = owner[p2];
-      const uint32_t w1 = bits[p1 >> 5][lane];
-      uint32_t w2 = bits[p2 >> 5][lane];
+        const uint32_t o1 = owner[p1], o2 = W2 ? owner[p2] : 0u;
+        const uint32_t w1 = bits[p1 >> 5][lane];
+        uint32_t w2 = W2 ? bits[p2 >> 5][lane] : 0u;
 #endif
 #ifndef TLCG_LANE_NO_SCHED_BARRIER
-      // (the reads issued together, before anything that consumes them or
-      // writes LDS: one round trip per expansion, not two)
-      __builtin_amdgcn_sched_barrier(0);
+        // (the reads issued together, before anything that consumes them or
+        // writes LDS: one round trip per expansion, not two)
+        __builtin_amdgcn_sched_barrier(0);
 #endif
-      const bool e1 = alive && r == 1, e2 = alive && crash;
-      // (the low half of an owner word: the code + 1; above it its features)
-      const bool in1 = (o1 & 0xFFFFu) == t + 1u, in2 = (o2 & 0xFFFFu) == t2 + 1u;
-      // a successor outside the code set: this component is not S's, the cascade
-      const bool out = (e1 && !in1) || (e2 && !in2);
+        const bool e1 = alive && r == 1, e2 = W2 && alive && crash;
+        // (the low half of an owner word: the code + 1; above it its features)
+        const bool in1 = (o1 & 0xFFFFu) == t + 1u, in2 = W2 && (o2 & 0xFFFFu) == t2 + 1u;
+        // a successor outside the code set: this component is not S's, the cascade
+        out = (e1 && !in1) || (e2 && !in2);
+        bool new2 = false;
 #if TLCG_LANE_FP_REG
-      // (a dense index is below 62: build_lane_phash)
-      const u64 b1 = 1ull << (uint32_t)(oe1 >> 32), b2 = 1ull << (uint32_t)(oe2 >> 32);
-      const bool new1 = e1 && in1 && !(fp & b1) && !out;
-      fp |= new1 ? b1 : 0ull;  // (the second sees the first's insert)
-      const bool new2 = e2 && in2 && !(fp & b2) && !out;
-      fp |= new2 ? b2 : 0ull;
+        // (a dense index is below 62: build_lane_phash)
+        const u64 b1 = 1ull << (uint32_t)(oe1 >> 32);
+        const bool new1 = e1 && in1 && !(fp & b1) && !out;
+        fp |= new1 ? b1 : 0ull;  // (the second sees the first's insert)
+        if constexpr (W2) {
+          const u64 b2 = 1ull << (uint32_t)(oe2 >> 32);
+          new2 = e2 && in2 && !(fp & b2) && !out;
+          fp |= new2 ? b2 : 0ull;
+        }
 #else
-      const uint32_t b1 = 1u << (p1 & 31), b2 = 1u << (p2 & 31);
-      const bool new1 = e1 && in1 && !(w1 & b1) && !out;
-      if ((p2 >> 5) == (p1 >> 5) && new1) w2 |= b1;  // (the second sees the first's insert)
-      const bool new2 = e2 && in2 && !(w2 & b2) && !out;
-      bits[p1 >> 5][lane] = new1 ? w1 | b1 : w1;
-      bits[p2 >> 5][lane] = new2 ? w2 | b2 : w2;
+        const uint32_t b1 = 1u << (p1 & 31);
+        const bool new1 = e1 && in1 && !(w1 & b1) && !out;
+        bits[p1 >> 5][lane] = new1 ? w1 | b1 : w1;
+        if constexpr (W2) {
+          const uint32_t b2 = 1u << (p2 & 31);
+          if ((p2 >> 5) == (p1 >> 5) && new1) w2 |= b1;  // (the second sees the first's insert)
+          new2 = e2 && in2 && !(w2 & b2) && !out;
+          bits[p2 >> 5][lane] = new2 ? w2 | b2 : w2;
+        }
 #endif
-      // the queue (the ring: a successor not inserted is overwritten or never
-      // read) and each new state's record at its position
+        // the queue (the ring: a successor not inserted is overwritten or never
+        // read) and each new state's record at its position
 #if TLCG_LANE_OWNER_RING
-      ring[tail & (R - 1)][lane] = o1;
-      ring[(tail + (new1 ? 1 : 0)) & (R - 1)][lane] = o2;
+        ring[tail & (R - 1)][lane] = o1;
+        if constexpr (W2) ring[(tail + (new1 ? 1 : 0)) & (R - 1)][lane] = o2;
 #else
-      ring[tail & (R - 1)][lane] = (uint16_t)t;
-      ring[(tail + (new1 ? 1 : 0)) & (R - 1)][lane] = (uint16_t)t2;
+        ring[tail & (R - 1)][lane] = (uint16_t)t;
+        if constexpr (W2) ring[(tail + (new1 ? 1 : 0)) & (R - 1)][lane] = (uint16_t)t2;
 #endif
 #ifndef TLCG_NO_STORE  // (experiment only: measures what the records cost)
-      __builtin_amdgcn_raw_buffer_store_b32(comp_record(t, head, action), rsrc,
-                                            new1 ? (int)((unsigned)tail * 256u + loff) : OOB, 0, 0);
-      __builtin_amdgcn_raw_buffer_store_b32(comp_record(t2, head, ACT_CRASH), rsrc,
-                                            new2 ? (int)((unsigned)(tail + (new1 ? 1 : 0)) * 256u + loff) : OOB, 0,
-                                            0);
+        __builtin_amdgcn_raw_buffer_store_b32(comp_record(t, head, action), rsrc,
+                                              new1 ? (int)((unsigned)tail * 256u + loff) : OOB, 0, 0);
+        if constexpr (W2)
+          __builtin_amdgcn_raw_buffer_store_b32(comp_record(t2, head, ACT_CRASH), rsrc,
+                                                new2 ? (int)((unsigned)(tail + (new1 ? 1 : 0)) * 256u + loff) : OOB,
+                                                0, 0);
 #endif
 #if TLCG_LANE_OWNER_RING
-      const uint32_t first_new = new1 ? o1 : o2;
+        first_new = W2 ? (new1 ? o1 : o2) : o1;
 #else
-      const ckey first_new = new1 ? t : t2;
+        first_new = W2 ? (new1 ? t : t2) : t;
 #endif
-      tail += (new1 ? 1 : 0) + (new2 ? 1 : 0);
+        tail += (new1 ? 1 : 0) + (new2 ? 1 : 0);
 #if TLCG_LANE_STEP_TAB
-      const int nsucc = (e1 ? 1 : 0) + (e2 ? 1 : 0) + (alive ? selfloop_count_tab(L, term_c, term) : 0);  // + stutters
+        const int nsucc = (e1 ? 1 : 0) + (e2 ? 1 : 0) + (alive ? selfloop_count_tab(L, term_c, term) : 0);  // + stutters
 #else
-      const int nsucc = (e1 ? 1 : 0) + (e2 ? 1 : 0) + (alive ? selfloop_count_c(L, ccon, s) : 0);  // + stutters
+        const int nsucc = (e1 ? 1 : 0) + (e2 ? 1 : 0) + (alive ? selfloop_count_c(L, ccon, s) : 0);  // + stutters
 #endif
-      lvgen += (unsigned)nsucc;
-      if constexpr (OD) lgen += alive ? 256u << (8 * (tail - tail0)) : 0u;  // new states this expansion discovered
-      // the inserted successors' invariants (first failing + 1; INV_UNKNOWN
-      // + 1: the rare branch settles it -- a failing feature, or an outcome
-      // table that left it to the programs)
-#if defined(TLCG_LANE_INV_UNCOND) && !defined(TLCG_NO_INV)  // (A/B: both evaluated, no branch)
-      const int q1 = check_invariants_cbt(L, ccon, t) + 1, q2 = check_invariants_cbt(L, ccon, t2) + 1;
-      int ev1 = new1 ? q1 : 0;
-      int ev2 = new2 ? q2 : 0;
-#elif TLCG_LANE_INV_FEAT && !defined(TLCG_NO_INV)
-      // (a feature of the code that is a failure in this component: which
-      // invariant and how, the rare branch says)
-      int ev1 = (new1 && ((o1 >> 16) & cmask)) ? INV_UNKNOWN + 1 : 0;
-      int ev2 = (new2 && ((o2 >> 16) & cmask)) ? INV_UNKNOWN + 1 : 0;
+        lvgen += (unsigned)nsucc;
+        if constexpr (OD) lgen += alive ? 256u << (8 * (tail - tail0)) : 0u;  // new states this expansion discovered
+        // the inserted successors' invariants (first failing + 1; INV_UNKNOWN
+        // + 1: the rare branch settles it -- a failing feature, or an outcome
+        // table that left it to the programs)
+#if TLCG_LANE_INV_FEAT && !defined(TLCG_NO_INV)
+        // (a feature of the code that is a failure in this component: which
+        // invariant and how, the rare branch says)
+        u1 = new1 && ((o1 >> 16) & cmask);
+        if constexpr (W2) u2 = new2 && ((o2 >> 16) & cmask);
 #elif !defined(TLCG_NO_INV)  // (TLCG_NO_INV: experiment only, measures what the invariants cost)
-      int ev1 = new1 ? check_invariants_cbt(L, ccon, t) + 1 : 0;
-      int ev2 = new2 ? check_invariants_cbt(L, ccon, t2) + 1 : 0;
+#ifdef TLCG_LANE_INV_UNCOND  // (A/B: both evaluated, no branch)
+        q1 = check_invariants_cbt(L, ccon, t) + 1;
+        if constexpr (W2) q2 = check_invariants_cbt(L, ccon, t2) + 1;
 #else
-      int ev1 = 0, ev2 = 0;
+        q1 = new1 ? check_invariants_cbt(L, ccon, t) + 1 : 0;
+        if constexpr (W2) q2 = new2 ? check_invariants_cbt(L, ccon, t2) + 1 : 0;
 #endif
-      // an action error (no successor from the failing action; the others
-      // still count, as k_expand), a deadlock and the successors' invariant
-      // events in one rare branch
-      const bool rare = alive && ((r == 2) | (nsucc == 0 && L.check_deadlock) | (ev1 != 0) | (ev2 != 0));
+        u1 = new1 && q1 != 0;
+        if constexpr (W2) u2 = new2 && q2 != 0;
+#endif
+        // an action error (no successor from the failing action; the others
+        // still count, as k_expand), a deadlock and the successors' invariant
+        // events in one rare branch, after the two forms join
+        dl = nsucc == 0 && L.check_deadlock;
+        rare = alive && ((r == 2) | dl | u1 | u2);
+      };
+#if TLCG_LANE_CRASH_SKIP
+      // BrokerCrash's guard on this lane's state; the second successor's code
+      // runs only when some live lane of the wave has one (one uniform branch)
+      if (__ballot(alive && crash_enabled_c(L, s))) expand(lane_with2<true>{});
+      else expand(lane_with2<false>{});
+#else
+      expand(lane_with2<true>{});
+#endif
       if (__ballot(rare)) {
         if (rare) {
+          int ev1 = u1 ? q1 : 0, ev2 = u2 ? q2 : 0;
+          ckey t2 = 0;
+          if (u2) crash_step_c(L, s, &t2);  // (u2: the form with BrokerCrash ran, and this lane's is enabled)
 #pragma nounroll
           for (int i = 0; i < 2; ++i) {
             if ((i ? ev2 : ev1) == INV_UNKNOWN + 1) {
@@ -382,7 +445,7 @@ __device__ __forceinline__ void component_lane_body(const CompArgs& a, const Lay
             }
           }
           u64 k = r == 2 ? make_comp_event(level + 1, idx0, head, action, EVK_ACTION_ERROR, action)
-                  : nsucc == 0 && L.check_deadlock ? make_comp_event(level + 1, idx0, head, 15, EVK_DEADLOCK, 0)
+                  : dl ? make_comp_event(level + 1, idx0, head, 15, EVK_DEADLOCK, 0)
                                                    : NO_EVENT;
           if (ev1) k = min(k, make_comp_event(level + 1, idx0, head, action, ((ev1 - 1) & 1) ? EVK_INV_ERROR : EVK_VIOLATION, (ev1 - 1) >> 1));
           if (ev2) k = min(k, make_comp_event(level + 1, idx0, head, ACT_CRASH, ((ev2 - 1) & 1) ? EVK_INV_ERROR : EVK_VIOLATION, (ev2 - 1) >> 1));
@@ -438,19 +501,23 @@ __device__ __forceinline__ void component_lane_body(const CompArgs& a, const Lay
       gen += OD ? lgen & 0xFFu : lgen;
       dist += (uint32_t)tail;
       nexp += (uint32_t)head;
-      ev = min(ev, (unsigned long long)lev);
+    }
+    // the batch's first event, once per wave (rare: not kept in a register
+    // across the batches, where it cost the BFS loop two VGPRs)
+    if (__ballot(fin && lev != NO_EVENT)) {
+      unsigned long long ev = fin ? (unsigned long long)lev : NO_EVENT;
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) ev = min(ev, (unsigned long long)__shfl_xor(ev, off));
+      if (lane == 0) atomicMin(a.event, ev);
     }
   }
   const u64 g64 = wave_sum_u64(gen), d64 = wave_sum_u64(dist), x64 = wave_sum_u64(nexp);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) ev = min(ev, (unsigned long long)__shfl_xor(ev, off));
   __syncthreads();
   const u64 so = a.nstripe > 1 ? (u64)(blockIdx.x % (unsigned)a.nstripe) * a.stripe : 0;  // this workgroup's copy
   if (lane == 0) {
     if (x64 && a.expansions) atomicAdd(&a.expansions[so], (unsigned long long)x64);
     if (g64) atomicAdd(&a.totals[so + 0], (unsigned long long)g64);
     if (d64) atomicAdd(&a.totals[so + 1], (unsigned long long)d64);
-    if (ev != NO_EVENT) atomicMin(a.event, ev);
   }
   if constexpr (OD)
     if (lane < 3 && lvl_sh[LV + lane]) atomicAdd(&a.outdeg[so + lane], lvl_sh[LV + lane]);
