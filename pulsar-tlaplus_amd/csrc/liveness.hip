@@ -31,18 +31,24 @@
 //      acyclic iff every state is removed.
 //   3. Counterexample: the shallowest stuck state (least packed word among
 //      the stuck states of the shallowest level) and its BFS path from Init;
-//      or, for a cycle, the states left after peeling are copied to the host,
-//      peeled again from the other side (states with no successor left), and
-//      walked from the shallowest one until a state repeats: the lasso is the
-//      BFS path to the repeated state plus the cycle back to it.
+//      or, for a cycle, the states left after peeling (k_lv_zero with left =
+//      1, gathered by k_lv_gather) are copied to the host, peeled again from
+//      the other side (states with no successor left), and walked from the
+//      shallowest one until a state repeats: the lasso is the BFS path to the
+//      repeated state plus the cycle back to it.
 // Counterexample choice and the output text are [TLC-ext] (TLC picks its
 // own); holds / fails, |G'|, its edge count and the shallowest stuck depth are
 // cross-checked with the oracle's Tarjan SCC restatement (oracle/tlc_oracle.c
 // -liveness).
 //
-// The second half of the file checks the properties a user defines -- <>Q,
-// []<>Q, P ~> Q over compiled state predicates -- with the same kernels for
-// the reachable graph and a seeded pass in index space (tlcg_check_property).
+// The file also checks the properties a user defines: <>Q, []<>Q, P ~> Q over
+// compiled state predicates (tlcg_check_property: the reachable graph, then a
+// seeded pass in index space) and [][A]_v over a compiled two-state program
+// (tlcg_check_action_property: the reachable graph, then every step once).
+// The three passes share two host drivers: Reach, the BFS of phase 1 with its
+// grow-and-redo loop, which all three run; and peel_verdict, phases 2 and 3,
+// which Termination and the property pass run through a view each (TermView,
+// PropView) that says how their G' is indexed.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -69,16 +75,20 @@ constexpr int LV_BLOCK = 256;
 
 enum LvFlag { LV_FPSET = 1, LV_STORE = 2, LV_EVAL = 4, LV_LOOKUP = 8 };
 
-struct LvCtr {
-  unsigned long long n;      // states of G' stored
-  unsigned long long edges;  // non-stuttering edges into not-P states
-  unsigned long long stuck;  // stuck states of the level just expanded
+// the counters of a G' (the reach BFS's, and the property pass's sub-BFS's)
+struct LvCtrHead {
+  unsigned long long n;      // states of G' stored (the sub-BFS: entries of `order`)
+  unsigned long long edges;  // non-stuttering edges into states of G'
+  unsigned long long stuck;  // stuck states, summed over the levels (the host takes the difference per level)
   unsigned long long next;   // entries appended to the next peel list
-  unsigned long long key_hi, key_lo, pick;  // least stuck state of a level, then its index
-  unsigned long long first_init;            // Init index of the first not-P initial state
+  unsigned long long key_hi, key_lo, pick;  // least flagged state of a level, then its stored index
+};
+struct LvCtr : LvCtrHead {
+  unsigned long long first_init;  // Init index of the first not-P initial state
   unsigned int flags;
   unsigned int pad;
 };
+static_assert(sizeof(LvCtrHead) == 56 && sizeof(LvCtr) == 72, "the kernels' counter layout");
 
 // G: the graph policy (liveness_graph.h)
 template <typename G>
@@ -355,28 +365,42 @@ __global__ __launch_bounds__(LV_BLOCK) void k_lv_expand(LvBufs<G> B, u64 a, u64 
   }
 }
 
-// the least stuck state of level [a, b): its high word, then its low word, then its index
-template <typename G>
-__global__ __launch_bounds__(LV_BLOCK) void k_lv_pick(LvBufs<G> B, u64 a, u64 b, int phase) {
-  using W = typename G::word;
+// The least flagged state (flag: a byte per stored state) of level [a, b) --
+// stored indices, or positions in `order` where there is one: its high word,
+// then its low word, then its stored index.  All three passes pick with it.
+template <typename W>
+__global__ __launch_bounds__(LV_BLOCK) void k_lv_pick(const W* store, const u32* order, const unsigned char* flag,
+                                                      LvCtrHead* ctr, u64 a, u64 b, int phase) {
   const u64 stride = (u64)gridDim.x * LV_BLOCK;
-  for (u64 g = a + (u64)blockIdx.x * LV_BLOCK + threadIdx.x; g < b; g += stride) {
-    if (!B.stuck[g]) continue;
-    const W s = B.store[g];
+  for (u64 i = a + (u64)blockIdx.x * LV_BLOCK + threadIdx.x; i < b; i += stride) {
+    const u64 g = order ? order[i] : i;
+    if (!flag[g]) continue;
+    const W s = store[g];
     const u64 hi = sizeof(W) == 8 ? 0 : (u64)((unsigned __int128)s >> 64), lo = (u64)s;
-    if (phase == 0) atomicMin(&B.ctr->key_hi, (unsigned long long)hi);
-    else if (phase == 1) { if (hi == B.ctr->key_hi) atomicMin(&B.ctr->key_lo, (unsigned long long)lo); }
-    else if (hi == B.ctr->key_hi && lo == B.ctr->key_lo) B.ctr->pick = g;
+    if (phase == 0) atomicMin(&ctr->key_hi, (unsigned long long)hi);
+    else if (phase == 1) { if (hi == ctr->key_hi) atomicMin(&ctr->key_lo, (unsigned long long)lo); }
+    else if (hi == ctr->key_hi && lo == ctr->key_lo) ctr->pick = g;
   }
 }
 
-// Kahn peeling: the states of in-degree 0 ...
+// the states at stored indices pos[0 .. n), or at those positions of `order`
+// (the host has checked that they lie inside the store)
+template <typename W>
+__global__ __launch_bounds__(LV_BLOCK) void k_lv_gather(const W* store, const u32* order, const u32* pos, u64 n,
+                                                        W* out) {
+  const u64 stride = (u64)gridDim.x * LV_BLOCK;
+  for (u64 i = (u64)blockIdx.x * LV_BLOCK + threadIdx.x; i < n; i += stride)
+    out[i] = store[order ? order[pos[i]] : pos[i]];
+}
+
+// Kahn peeling: the states of in-degree 0 (after the rounds, with left = 1:
+// the ones that kept an in-edge, which lie on or after a cycle) ...
 template <typename G>
-__global__ __launch_bounds__(LV_BLOCK) void k_lv_zero(LvBufs<G> B, u64 n, u32* list) {
+__global__ __launch_bounds__(LV_BLOCK) void k_lv_zero(LvBufs<G> B, u64 n, u32* list, int left) {
   const u64 stride = (u64)gridDim.x * LV_BLOCK;
   for (u64 base = (u64)blockIdx.x * LV_BLOCK; base < n; base += stride) {
     const u64 g = base + threadIdx.x;
-    const bool z = g < n && B.indeg[B.slot_of[g]] == 0;
+    const bool z = g < n && (B.indeg[B.slot_of[g]] == 0) != (left != 0);
     u64 at = 0;
     block_claim<1>(&z, &at, &B.ctr->next);
     if (z) list[at] = (u32)g;
@@ -430,19 +454,6 @@ __global__ __launch_bounds__(LV_BLOCK) void k_lv_peel(LvBufs<G> B, const u32* li
   }
 }
 
-// the states left after peeling (on or after a cycle): their indices
-template <typename G>
-__global__ __launch_bounds__(LV_BLOCK) void k_lv_left(LvBufs<G> B, u64 n, u32* list) {
-  const u64 stride = (u64)gridDim.x * LV_BLOCK;
-  for (u64 base = (u64)blockIdx.x * LV_BLOCK; base < n; base += stride) {
-    const u64 g = base + threadIdx.x;
-    const bool z = g < n && B.indeg[B.slot_of[g]] != 0;
-    u64 at = 0;
-    block_claim<1>(&z, &at, &B.ctr->next);
-    if (z) list[at] = (u32)g;
-  }
-}
-
 // TLCG_LV_GRID=n caps the grid of every kernel of the pass (a test hook: one
 // block then takes every grid-stride chunk); 0 or unset: no cap
 unsigned lv_grid_cap() {
@@ -457,8 +468,10 @@ unsigned lv_grid(u64 n, unsigned cap) {
 
 struct DevMem {
   std::vector<void*> ptrs;
-  ~DevMem() {
+  ~DevMem() { clear(); }
+  void clear() {
     for (void* p : ptrs) hipFree(p);
+    ptrs.clear();
   }
   template <typename T>
   bool alloc(T** p, u64 count) {
@@ -477,6 +490,26 @@ struct DevMem {
       return -4;                                                                 \
     }                                                                            \
   } while (0)
+
+// device time of a stretch of launches on the null stream
+struct LvTimer {
+  hipEvent_t a = nullptr, b = nullptr;
+  ~LvTimer() {
+    if (a) hipEventDestroy(a);
+    if (b) hipEventDestroy(b);
+  }
+  hipError_t start() {
+    hipError_t e = hipSuccess;
+    if (!a && (e = hipEventCreate(&a)) != hipSuccess) return e;
+    if (!b && (e = hipEventCreate(&b)) != hipSuccess) return e;
+    return hipEventRecord(a, 0);
+  }
+  hipError_t stop(float* ms) {
+    hipError_t e = hipEventRecord(b, 0);
+    if (e == hipSuccess) e = hipEventSynchronize(b);
+    return e == hipSuccess ? hipEventElapsedTime(ms, a, b) : e;
+  }
+};
 
 struct LvTrace {
   std::vector<u128> states;
@@ -508,250 +541,359 @@ int path_to(const LvBufs<G>& B, const G& hg, u64 g, LvTrace* tr, std::string* er
   return 0;
 }
 
+// a pass's counters as the device has them now
+template <typename C>
+int read_ctr(C* h, const C* d_ctr, std::string* err) {
+  LV_CHECK(hipMemcpy(h, d_ctr, sizeof *h, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// what a pass calls itself and the states it counts, for its messages
+struct LvNames {
+  const char *prefix, *check, *counted;
+};
+constexpr LvNames NM_LIVENESS{"liveness", "the liveness check", "not-P states"};
+constexpr LvNames NM_PROPERTY{"property", "the property check", "reachable states"};
+constexpr LvNames NM_ACTION{"action property", "the action property check", "reachable states"};
+
+// Phase 1 of every pass: the BFS over G' (for ReachAll: over the whole graph)
+// into buffers sized by opts, redone with a store and FPSet four times as
+// large when either fills up, and with half the capacity when the device
+// cannot hold them.  After run() returns 0: B, h (the counters as last read),
+// the levels and ms (the kernel time of the attempt that fit) stand; mem owns
+// every buffer and tm is free for the caller's own stretches.
+template <typename G>
+struct Reach {
+  using W = typename G::word;
+  DevMem mem;
+  LvBufs<G> B;
+  LvCtr h;
+  std::vector<u64> level_base;   // level l is store[level_base[l], level_base[l + 1]); the last entry repeats
+  std::vector<u64> level_stuck;  // stuck states per level
+  float ms = 0.f;
+  LvTimer tm;
+  const unsigned grid_cap = lv_grid_cap();
+  unsigned grid(u64 n) const { return lv_grid(n, grid_cap); }
+
+  // dg: the graph as the kernels read it; fair: what makes a state stuck;
+  // extra(mem, cap): allocates the pass's own buffers that are sized by the
+  // capacity (false: they do not fit, which halves the capacity as well)
+  template <typename Extra>
+  int run(const G& dg, const tlcg_opts* o, int fair, const LvNames& nm, Extra extra, std::string* err) {
+    const std::string pre = std::string(nm.prefix) + ": ";
+    u64 cap = o && o->state_capacity ? o->state_capacity : (u64)1 << 22;
+    int log2 = o && o->log2_fpset_slots > 0 ? o->log2_fpset_slots : 0;
+    for (int attempt = 0;; ++attempt) {
+      if (cap >= (1ull << 32) - 1) {
+        *err = std::string(nm.check) + " indexes states with 32 bits: more than 2^32 - 1 " + nm.counted;
+        return -5;
+      }
+      int lg = log2;
+      if (lg <= 0 || attempt > 0) {
+        lg = 10;
+        while ((1ull << lg) < 2 * cap) ++lg;
+      }
+      if (lg > 32) lg = 32;
+      mem.clear();  // (the last attempt's buffers go before this one's come)
+      B.g = dg;
+      B.log2 = lg;
+      B.cap = cap;
+      const u64 nslots = 1ull << lg;
+      if (!mem.alloc(&B.slots, nslots * (sizeof(W) / 8)) || !mem.alloc(&B.store, cap) || !mem.alloc(&B.parent, cap) ||
+          !mem.alloc(&B.slot_of, cap) || !mem.alloc(&B.gidx_of, nslots) || !mem.alloc(&B.indeg, nslots) ||
+          !mem.alloc(&B.stuck, cap) || !mem.alloc(&B.ctr, 1) || !extra(mem, cap)) {
+        if (cap > (1ull << 20) && attempt < 8) {
+          // what HBM holds beside the caller's other buffers: a smaller start,
+          // grown x4 below only if G' needs it
+          cap /= 2;
+          log2 = 0;
+          continue;
+        }
+        *err = pre + "device allocation failed (" + std::to_string(cap) + " states, 2^" + std::to_string(lg) +
+               " FPSet slots)";
+        return -5;
+      }
+      LV_CHECK(hipMemset(B.slots, 0, nslots * sizeof(W)));
+      LV_CHECK(hipMemset(B.indeg, 0, nslots * sizeof(u32)));
+      h = LvCtr{};
+      h.first_init = ~0ull;
+      LV_CHECK(hipMemcpy(B.ctr, &h, sizeof h, hipMemcpyHostToDevice));
+      auto grow = [&]() { return (h.flags & (LV_FPSET | LV_STORE)) != 0; };
+      LV_CHECK(tm.start());
+      k_lv_init<G><<<grid(dg.n_init()), LV_BLOCK>>>(B);
+      LV_CHECK(hipGetLastError());
+      if (read_ctr(&h, B.ctr, err)) return -4;
+      level_base = {0, std::min<u64>(h.n, cap)};
+      level_stuck.clear();
+      bool again = grow();
+      while (!again && level_base.back() > level_base[level_base.size() - 2]) {
+        const u64 a = level_base[level_base.size() - 2], b = level_base.back(), stuck_before = h.stuck;
+        k_lv_expand<G><<<grid(b - a), LV_BLOCK>>>(B, a, b, fair);
+        LV_CHECK(hipGetLastError());
+        if (read_ctr(&h, B.ctr, err)) return -4;
+        if (h.flags & LV_EVAL) {
+          *err = pre + "an evaluation error while computing a successor (run the safety check first)";
+          return -6;
+        }
+        if ((again = grow())) break;
+        level_stuck.push_back(h.stuck - stuck_before);  // (the device's count runs on over the levels)
+        level_base.push_back(h.n);
+      }
+      LV_CHECK(tm.stop(&ms));
+      if (!again) return 0;
+      cap *= 4;  // redo with a larger store and FPSet
+    }
+  }
+};
+
+// the least flagged state of level [a, b) into h->pick (~0: none); d_ctr / h:
+// a pass's counters on the device and as last read
+template <typename W, typename C>
+int pick_least(const W* store, const u32* order, const unsigned char* flag, C* d_ctr, C* h, u64 a, u64 b,
+               unsigned grid, std::string* err) {
+  h->key_hi = h->key_lo = h->pick = ~0ull;
+  LV_CHECK(hipMemcpy(d_ctr, h, sizeof *h, hipMemcpyHostToDevice));
+  for (int ph = 0; ph < 3; ++ph) k_lv_pick<W><<<grid, LV_BLOCK>>>(store, order, flag, d_ctr, a, b, ph);
+  LV_CHECK(hipGetLastError());
+  LV_CHECK(hipMemcpy(h, d_ctr, sizeof *h, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// Phases 2 and 3 over a G' that has been built level by level: Kahn peeling,
+// the verdict into *lv and the counterexample into *tr.  level / level_stuck:
+// G' levels and their stuck states, as Reach keeps them; la, lb: peel lists of
+// level.back() entries each; ms_before: kernel time so far, to which the time
+// since the caller's r.tm.start() is added.  V, the view of the pass's G':
+//   r, d_ctr, h      its Reach; its counters on the device and as last read
+//   order, n_all     G' in BFS order as stored indices (null: G' is the store), their bound
+//   stuck            the stuck byte per stored state
+//   zero(n, list, left), peel(list, n, next)   launch the peel kernels
+//   path(g, tr, err), stutter(tr, err)   the trace to stored state g, the no-fairness trace
+template <typename G, typename V>
+int peel_verdict(V& v, const G& hg, int fair, const std::vector<u64>& level, const std::vector<u64>& level_stuck,
+                 u32* la, u32* lb, float ms_before, const LvNames& nm, tlcg_liveness* lv, LvTrace* tr,
+                 std::string* err) {
+  using W = typename G::word;
+  const std::string pre = std::string(nm.prefix) + ": ";
+  auto& r = v.r;
+  auto& h = v.h;
+  const u64 n = level.back();
+  LV_CHECK(hipMemset(&v.d_ctr->next, 0, sizeof(unsigned long long)));
+  v.zero(n, la, 0);
+  LV_CHECK(hipGetLastError());
+  if (read_ctr(&h, v.d_ctr, err)) return -4;
+  u64 removed = 0, cur = h.next;
+  int rounds = 0;
+  while (cur) {
+    removed += cur;
+    ++rounds;
+    LV_CHECK(hipMemset(&v.d_ctr->next, 0, sizeof(unsigned long long)));
+    v.peel(la, cur, lb);
+    LV_CHECK(hipGetLastError());
+    if (read_ctr(&h, v.d_ctr, err)) return -4;
+    if (h.flags & LV_LOOKUP) {
+      *err = pre + "a successor in G' is missing from the FPSet";
+      return -6;
+    }
+    cur = h.next;
+    std::swap(la, lb);
+  }
+  float ms = 0.f;
+  LV_CHECK(r.tm.stop(&ms));
+  lv->stuck = 0;
+  for (u64 x : level_stuck) lv->stuck += x;
+  lv->peel_rounds = rounds;
+  lv->on_cycles = n - removed;
+  lv->kernel_ms = ms_before + ms;
+  if (lv->stuck) {
+    lv->holds = 0;
+    lv->kind = TLCG_LIVE_STUTTERING;
+    // without fairness every state of G' may stutter forever; with it, the
+    // least stuck state of the shallowest level that has one
+    if (fair == TLCG_FAIR_NONE) return v.stutter(tr, err);
+    size_t l = 0;
+    while (level_stuck[l] == 0) ++l;
+    const u64 a = level[l], b = level[l + 1];
+    if (const int rc = pick_least(r.B.store, v.order, v.stuck, v.d_ctr, &h, a, b, r.grid(b - a), err)) return rc;
+    if (h.pick >= v.n_all) {
+      *err = pre + "no stuck state found in its level";
+      return -6;
+    }
+    return v.path(h.pick, tr, err);
+  }
+  if (removed == n) {
+    lv->holds = 1;
+    lv->kind = TLCG_LIVE_HOLDS;
+    return 0;
+  }
+  // a cycle: the states left after peeling, by their place in G' BFS order
+  lv->holds = 0;
+  lv->kind = TLCG_LIVE_CYCLE;
+  const u64 left = n - removed;
+  if (left > (1ull << 26)) {
+    *err = pre + std::to_string(left) + " states lie on or after cycles; the lasso extraction takes at most 2^26";
+    return -5;
+  }
+  LV_CHECK(hipMemset(&v.d_ctr->next, 0, sizeof(unsigned long long)));
+  v.zero(n, la, 1);
+  LV_CHECK(hipGetLastError());
+  std::vector<u32> pos(left), ord_h(v.order ? n : 0);
+  std::vector<W> st(left);
+  LV_CHECK(hipMemcpy(pos.data(), la, left * sizeof(u32), hipMemcpyDeviceToHost));
+  if (v.order) LV_CHECK(hipMemcpy(ord_h.data(), v.order, n * sizeof(u32), hipMemcpyDeviceToHost));
+  std::sort(pos.begin(), pos.end());
+  auto stored = [&](u64 p) -> u64 { return v.order ? ord_h[p] : p; };
+  for (u64 i = 0; i < left; ++i)
+    if (pos[i] >= n || stored(pos[i]) >= v.n_all) {
+      *err = pre + "a state left after peeling lies outside G'";
+      return -6;
+    }
+  // their states, gathered on the device in that order and copied at once
+  W* d_st = nullptr;
+  if (!r.mem.alloc(&d_st, left)) {
+    *err = pre + "device allocation failed (the states left after peeling)";
+    return -5;
+  }
+  LV_CHECK(hipMemcpy(la, pos.data(), left * sizeof(u32), hipMemcpyHostToDevice));
+  k_lv_gather<W><<<r.grid(left), LV_BLOCK>>>(r.B.store, v.order, la, left, d_st);
+  LV_CHECK(hipGetLastError());
+  LV_CHECK(hipMemcpy(st.data(), d_st, left * sizeof(W), hipMemcpyDeviceToHost));
+  // (the walk stays among the states left, so a ReachAll host graph, which
+  // has no P or Q of its own, serves it)
+  u64 entry = 0;
+  std::vector<u128> cyc;
+  std::vector<int> cyc_act;
+  int back = -1;
+  if (lasso_walk(hg, st, pos, &entry, &cyc, &cyc_act, &back, err) != 0) return -6;
+  // the path to the cycle's entry, then around the cycle back to it
+  if (const int rc = v.path(stored(entry), tr, err)) return rc;
+  tr->loop_to = (int)tr->states.size() - 1;
+  tr->states.insert(tr->states.end(), cyc.begin(), cyc.end());
+  tr->actions.insert(tr->actions.end(), cyc_act.begin(), cyc_act.end());
+  tr->back_action = back;
+  return 0;
+}
+
+// Termination's G' is the store itself: stored indices, in-degree by FPSet slot
+template <typename G>
+struct TermView {
+  Reach<G>& r;
+  const G& hg;
+  LvCtr* d_ctr;
+  LvCtr& h;
+  const u32* order;
+  u64 n_all;
+  const unsigned char* stuck;
+  void zero(u64 n, u32* list, int left) { k_lv_zero<G><<<r.grid(n), LV_BLOCK>>>(r.B, n, list, left); }
+  void peel(const u32* list, u64 n, u32* next) { k_lv_peel<G><<<r.grid(n), LV_BLOCK>>>(r.B, list, n, next); }
+  int path(u64 g, LvTrace* tr, std::string* err) { return path_to(r.B, hg, g, tr, err); }
+  // the first not-P initial state in Init order, then stuttering
+  int stutter(LvTrace* tr, std::string*) {
+    tr->states.push_back((u128)hg.init(h.first_init));
+    tr->actions.push_back(TLCG_ACT_INIT);
+    return 0;
+  }
+};
+
 // dg: the graph as the kernels read it, hg: as the host reads it (the same
 // object for ModelGraph; device and host copies of the arrays for ExplicitGraph)
 template <typename G>
 int run_liveness(const G& dg, const G& hg, const tlcg_opts* o, int fair, tlcg_liveness* out, LvTrace* tr,
                  std::string* err) {
-  using W = typename G::word;
-  const unsigned grid_cap = lv_grid_cap();
-  auto grid_for = [grid_cap](u64 n) { return lv_grid(n, grid_cap); };
-  u64 cap = o && o->state_capacity ? o->state_capacity : (u64)1 << 22;
-  int log2 = o && o->log2_fpset_slots > 0 ? o->log2_fpset_slots : 0;
-  hipEvent_t e0, e1;
-  LV_CHECK(hipEventCreate(&e0));
-  LV_CHECK(hipEventCreate(&e1));
-  struct EvGuard {
-    hipEvent_t a, b;
-    ~EvGuard() {
-      hipEventDestroy(a);
-      hipEventDestroy(b);
-    }
-  } evg{e0, e1};
-  for (int attempt = 0;; ++attempt) {
-    if (cap >= (1ull << 32) - 1) {
-      *err = "the liveness check indexes states with 32 bits: more than 2^32 - 1 not-P states";
-      return -5;
-    }
-    int lg = log2;
-    if (lg <= 0 || attempt > 0) {
-      lg = 10;
-      while ((1ull << lg) < 2 * cap) ++lg;
-    }
-    if (lg > 32) lg = 32;
-    DevMem mem;
-    LvBufs<G> B;
-    B.g = dg;
-    B.log2 = lg;
-    B.cap = cap;
-    const u64 nslots = 1ull << lg;
-    if (!mem.alloc(&B.slots, nslots * (sizeof(W) / 8)) || !mem.alloc(&B.store, cap) || !mem.alloc(&B.parent, cap) ||
-        !mem.alloc(&B.slot_of, cap) || !mem.alloc(&B.gidx_of, nslots) || !mem.alloc(&B.indeg, nslots) ||
-        !mem.alloc(&B.stuck, cap) || !mem.alloc(&B.ctr, 1)) {
-      if (cap > (1ull << 20) && attempt < 8) {
-        // what HBM holds beside the caller's other buffers: a smaller start,
-        // grown x4 below only if G' needs it
-        cap /= 2;
-        log2 = 0;
-        continue;
-      }
-      *err = "liveness: device allocation failed (" + std::to_string(cap) + " states, 2^" + std::to_string(lg) +
-             " FPSet slots)";
-      return -5;
-    }
-    LV_CHECK(hipMemset(B.slots, 0, nslots * sizeof(W)));
-    LV_CHECK(hipMemset(B.indeg, 0, nslots * sizeof(u32)));
-    LvCtr h{};
-    h.first_init = ~0ull;
-    LV_CHECK(hipMemcpy(B.ctr, &h, sizeof h, hipMemcpyHostToDevice));
-    auto read_ctr = [&]() -> int {
-      LV_CHECK(hipMemcpy(&h, B.ctr, sizeof h, hipMemcpyDeviceToHost));
-      return 0;
-    };
-    auto grow = [&]() {
-      return (h.flags & (LV_FPSET | LV_STORE)) != 0;
-    };
-    float ms_total = 0.f, ms = 0.f;
-    LV_CHECK(hipEventRecord(e0, 0));
-    k_lv_init<G><<<grid_for(hg.n_init()), LV_BLOCK>>>(B);
-    LV_CHECK(hipGetLastError());
-    if (read_ctr()) return -4;
-    std::vector<u64> level_base{0, std::min<u64>(h.n, cap)}, level_stuck;
-    bool again = grow();
-    while (!again && level_base.back() > level_base[level_base.size() - 2]) {
-      const u64 a = level_base[level_base.size() - 2], b = level_base.back();
-      LV_CHECK(hipMemset(&B.ctr->stuck, 0, sizeof(unsigned long long)));
-      k_lv_expand<G><<<grid_for(b - a), LV_BLOCK>>>(B, a, b, fair);
-      LV_CHECK(hipGetLastError());
-      if (read_ctr()) return -4;
-      if (h.flags & LV_EVAL) {
-        *err = "liveness: an evaluation error while computing a successor (run the safety check first)";
-        return -6;
-      }
-      if ((again = grow())) break;
-      level_stuck.push_back(h.stuck);
-      level_base.push_back(h.n);
-    }
-    LV_CHECK(hipEventRecord(e1, 0));
-    LV_CHECK(hipEventSynchronize(e1));
-    LV_CHECK(hipEventElapsedTime(&ms, e0, e1));
-    ms_total += ms;
-    if (again) {
-      cap *= 4;
-      continue;  // redo with a larger store and FPSet
-    }
-    const u64 n = h.n;
-    out->states_notp = n;
-    out->init_notp = level_base[1];
-    out->edges_notp = h.edges;
-    out->depth = (int32_t)(level_base.size() - 2);  // (the last entry repeats: the empty level that ended the BFS)
-    out->stuck = 0;
-    for (u64 x : level_stuck) out->stuck += x;
-    // 2. Kahn peeling
-    u32 *la = nullptr, *lb = nullptr;
-    if (!mem.alloc(&la, n) || !mem.alloc(&lb, n)) {
-      *err = "liveness: device allocation failed (peel lists)";
-      return -5;
-    }
-    LV_CHECK(hipEventRecord(e0, 0));
-    LV_CHECK(hipMemset(&B.ctr->next, 0, sizeof(unsigned long long)));
-    k_lv_zero<G><<<grid_for(n), LV_BLOCK>>>(B, n, la);
-    LV_CHECK(hipGetLastError());
-    if (read_ctr()) return -4;
-    u64 removed = 0, cur = h.next;
-    int rounds = 0;
-    while (cur) {
-      removed += cur;
-      ++rounds;
-      LV_CHECK(hipMemset(&B.ctr->next, 0, sizeof(unsigned long long)));
-      k_lv_peel<G><<<grid_for(cur), LV_BLOCK>>>(B, la, cur, lb);
-      LV_CHECK(hipGetLastError());
-      if (read_ctr()) return -4;
-      if (h.flags & LV_LOOKUP) {
-        *err = "liveness: a successor in G' is missing from the FPSet";
-        return -6;
-      }
-      cur = h.next;
-      std::swap(la, lb);
-    }
-    LV_CHECK(hipEventRecord(e1, 0));
-    LV_CHECK(hipEventSynchronize(e1));
-    LV_CHECK(hipEventElapsedTime(&ms, e0, e1));
-    ms_total += ms;
-    out->peel_rounds = rounds;
-    out->on_cycles = n - removed;
-    out->kernel_ms = ms_total;
-    // 3. verdict and counterexample
-    if (out->stuck && fair == TLCG_FAIR_NONE) {
-      // every state of G' may stutter forever: the shortest counterexample is
-      // the first not-P initial state in Init order, then stuttering
-      out->holds = 0;
-      out->kind = TLCG_LIVE_STUTTERING;
-      tr->states.push_back((u128)hg.init(h.first_init));
-      tr->actions.push_back(TLCG_ACT_INIT);
-      return 0;
-    }
-    if (out->stuck) {
-      out->holds = 0;
-      out->kind = TLCG_LIVE_STUTTERING;
-      size_t lv = 0;
-      while (level_stuck[lv] == 0) ++lv;
-      const u64 a = level_base[lv], b = level_base[lv + 1];
-      h.key_hi = h.key_lo = ~0ull;
-      h.pick = ~0ull;
-      LV_CHECK(hipMemcpy(B.ctr, &h, sizeof h, hipMemcpyHostToDevice));
-      for (int ph = 0; ph < 3; ++ph) k_lv_pick<G><<<grid_for(b - a), LV_BLOCK>>>(B, a, b, ph);
-      LV_CHECK(hipGetLastError());
-      if (read_ctr()) return -4;
-      if (h.pick == ~0ull) {
-        *err = "liveness: no stuck state found in its level";
-        return -6;
-      }
-      return path_to(B, hg, h.pick, tr, err);
-    }
-    if (removed == n) {
-      out->holds = 1;
-      out->kind = TLCG_LIVE_HOLDS;
-      return 0;
-    }
-    // a cycle: copy the states left after peeling to the host
-    out->holds = 0;
-    out->kind = TLCG_LIVE_CYCLE;
-    const u64 left = n - removed;
-    if (left > (1ull << 26)) {
-      *err = "liveness: " + std::to_string(left) + " states lie on or after cycles; the lasso extraction takes at most 2^26";
-      return -5;
-    }
-    LV_CHECK(hipMemset(&B.ctr->next, 0, sizeof(unsigned long long)));
-    k_lv_left<G><<<grid_for(n), LV_BLOCK>>>(B, n, la);
-    LV_CHECK(hipGetLastError());
-    std::vector<u32> idx(left);
-    std::vector<W> st(left);
-    LV_CHECK(hipMemcpy(idx.data(), la, left * sizeof(u32), hipMemcpyDeviceToHost));
-    std::sort(idx.begin(), idx.end());
-    for (u64 i = 0; i < left; ++i) LV_CHECK(hipMemcpy(&st[i], B.store + idx[i], sizeof(W), hipMemcpyDeviceToHost));
-    u64 g_entry = 0;
-    std::vector<u128> cyc;
-    std::vector<int> cyc_act;
-    int back = -1;
-    if (lasso_walk(hg, st, idx, &g_entry, &cyc, &cyc_act, &back, err) != 0) return -6;
-    // the BFS path to the cycle's entry, then around the cycle back to it
-    if (path_to(B, hg, g_entry, tr, err)) return -4;
-    tr->loop_to = (int)tr->states.size() - 1;
-    tr->states.insert(tr->states.end(), cyc.begin(), cyc.end());
-    tr->actions.insert(tr->actions.end(), cyc_act.begin(), cyc_act.end());
-    tr->back_action = back;
-    return 0;
+  Reach<G> r;
+  if (const int rc = r.run(dg, o, fair, NM_LIVENESS, [](DevMem&, u64) { return true; }, err)) return rc;
+  const u64 n = r.h.n;
+  out->states_notp = n;
+  out->init_notp = r.level_base[1];
+  out->edges_notp = r.h.edges;
+  out->depth = (int32_t)(r.level_base.size() - 2);  // (the last entry repeats: the empty level that ended the BFS)
+  u32 *la = nullptr, *lb = nullptr;
+  if (!r.mem.alloc(&la, n) || !r.mem.alloc(&lb, n)) {
+    *err = "liveness: device allocation failed (peel lists)";
+    return -5;
   }
+  LV_CHECK(r.tm.start());
+  TermView<G> v{r, hg, r.B.ctr, r.h, nullptr, n, r.B.stuck};
+  return peel_verdict(v, hg, fair, r.level_base, r.level_stuck, la, lb, r.ms, NM_LIVENESS, out, tr, err);
 }
 
-// the counterexample into the caller's arrays
-void lv_copy_out(const LvTrace& tr, int words, tlcg_liveness* out, uint64_t* states, int32_t* actions, int32_t cap,
-                 int32_t* len) {
-  out->trace_len = (int32_t)tr.states.size();
-  out->loop_to = tr.loop_to;
-  out->back_action = tr.back_action;
+// the counterexample into the caller's arrays; returns its whole length
+int32_t trace_copy_out(const LvTrace& tr, int words, uint64_t* states, int32_t* actions, int32_t cap, int32_t* len) {
+  const int32_t all = (int32_t)tr.states.size();
   if (states && actions && len) {
-    const int32_t n = std::min<int32_t>(cap, out->trace_len);
+    const int32_t n = std::min<int32_t>(cap, all);
     for (int32_t i = 0; i < n; ++i) {
       split_words(tr.states[i], states + (size_t)i * words, words);
       actions[i] = tr.actions[i];
     }
     *len = n;
   }
+  return all;
+}
+void lv_copy_out(const LvTrace& tr, int words, tlcg_liveness* out, uint64_t* states, int32_t* actions, int32_t cap,
+                 int32_t* len) {
+  out->trace_len = trace_copy_out(tr, words, states, actions, cap, len);
+  out->loop_to = tr.loop_to;
+  out->back_action = tr.back_action;
+}
+
+// what an extern "C" entry returns when it fails: the message into the caller's buffer
+struct Fail {
+  char* err;
+  int32_t cap;
+  int operator()(int rc, const std::string& e) const {
+    if (err && cap > 0) std::snprintf(err, (size_t)cap, "%s", e.c_str());
+    return rc;
+  }
+};
+
+// the selftest entries refuse a malformed graph before the device is touched
+bool graph_ok(const uint32_t* row, const uint32_t* col, uint32_t n, uint32_t n_init, std::string* err) {
+  ExplicitGraph<u64> shape{};
+  return explicit_graph_shape(row, col, n, n_init, &shape, err);
 }
 
 template <typename W>
 int run_model(const HostModel& hm, const tlcg_opts* o, int fair, tlcg_liveness* out, LvTrace* tr, std::string* err) {
-  ModelGraph<W> g;
-  g.L = hm.L;
-  g.n_init_ = hm.n_init;
+  const ModelGraph<W> g{hm.L, hm.n_init};
   return run_liveness(g, g, o, fair, out, tr, err);
 }
 
-// the caller's CSR graph: checked, copied to the device, walked
-template <typename W>
-int run_explicit(const uint32_t* row, const uint32_t* col, const uint8_t* is_p, uint32_t n, uint32_t n_init,
-                 const tlcg_opts* o, int fair, tlcg_liveness* out, LvTrace* tr, std::string* err) {
-  ExplicitGraph<W> hg{};
-  if (!explicit_graph_shape(row, col, n, n_init, &hg, err)) return -1;
-  hg.row = row;
-  hg.col = col;
-  hg.p = is_p;
-  DevMem mem;
-  uint32_t *d_row = nullptr, *d_col = nullptr;
-  unsigned char* d_p = nullptr;
-  if (!mem.alloc(&d_row, (u64)n + 1) || !mem.alloc(&d_col, row[n]) || !mem.alloc(&d_p, n)) {
+// n values of the caller's (src null: room for them only) into device memory that mem owns
+template <typename T>
+int upload(DevMem& mem, const T* src, u64 n, const T** dst, std::string* err) {
+  T* d = nullptr;
+  if (!mem.alloc(&d, n)) {
     *err = "graph: device allocation failed";
     return -5;
   }
-  LV_CHECK(hipMemcpy(d_row, row, ((size_t)n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
-  if (row[n]) LV_CHECK(hipMemcpy(d_col, col, (size_t)row[n] * sizeof(uint32_t), hipMemcpyHostToDevice));
-  if (n) LV_CHECK(hipMemcpy(d_p, is_p, n, hipMemcpyHostToDevice));
-  ExplicitGraph<W> dg = hg;
-  dg.row = d_row;
-  dg.col = d_col;
-  dg.p = d_p;
+  if (n && src) LV_CHECK(hipMemcpy(d, src, n * sizeof(T), hipMemcpyHostToDevice));
+  *dst = d;
+  return 0;
+}
+
+// the caller's CSR graph, checked: *hg over the caller's arrays, *dg over
+// copies of them in device memory; both without a P
+template <typename W>
+int upload_graph(const uint32_t* row, const uint32_t* col, uint32_t n, uint32_t n_init, DevMem& mem,
+                 ExplicitGraph<W>* hg, ExplicitGraph<W>* dg, std::string* err) {
+  *hg = ExplicitGraph<W>{};
+  if (!explicit_graph_shape(row, col, n, n_init, hg, err)) return -1;
+  hg->row = row;
+  hg->col = col;
+  *dg = *hg;
+  if (const int rc = upload(mem, row, (u64)n + 1, &dg->row, err)) return rc;
+  return upload(mem, col, row[n], &dg->col, err);
+}
+
+template <typename W>
+int run_explicit(const uint32_t* row, const uint32_t* col, const uint8_t* is_p, uint32_t n, uint32_t n_init,
+                 const tlcg_opts* o, int fair, tlcg_liveness* out, LvTrace* tr, std::string* err) {
+  DevMem mem;
+  ExplicitGraph<W> hg, dg;
+  if (const int rc = upload_graph(row, col, n, n_init, mem, &hg, &dg, err)) return rc;
+  hg.p = is_p;
+  if (const int rc = upload(mem, is_p, n, &dg.p, err)) return rc;
   return run_liveness(dg, hg, o, fair, out, tr, err);
 }
 
@@ -775,9 +917,10 @@ int run_explicit(const uint32_t* row, const uint32_t* col, const uint8_t* is_p, 
 //      bit -- the lane that sets it appends the index to `order` and writes
 //      the G' parent.  No second FPSet, no second store;
 //   5. Kahn peeling over `order` with the per-index in-degree (k_pp_zero,
-//      k_pp_peel, k_pp_left);
+//      k_pp_peel);
 //   6. counterexample: the G' path (or the lasso) back to its root seed,
 //      behind the reach BFS path from Init to that seed.
+// 1 is Reach, 5 and 6 are peel_verdict through PropView.
 // Per reachable state beside the reach pass's buffers: class byte, member
 // bit, order entry, G' parent, two peel list entries: 21.1 B.  The in-degree
 // and stuck arrays of the reach pass are reused, indexed by stored index (the
@@ -819,17 +962,13 @@ struct ByteClass {
   }
 };
 
-struct PpCtr {
-  unsigned long long n;      // states of G' (entries of `order`)
-  unsigned long long edges;  // non-stuttering edges into states of G'
-  unsigned long long stuck;  // stuck states of the level just expanded
-  unsigned long long next;   // entries appended to the next peel list
-  unsigned long long key_hi, key_lo, pick;  // least stuck state of a level, then its stored index
-  unsigned long long first_seed;            // least stored index of a seed
-  unsigned long long first_err;             // least stored index of a state where P or Q fails to evaluate
+struct PpCtr : LvCtrHead {
+  unsigned long long first_seed;  // least stored index of a seed
+  unsigned long long first_err;   // least stored index of a state where P or Q fails to evaluate
   unsigned int flags;
   unsigned int pad;
 };
+static_assert(sizeof(PpCtr) == 80, "the kernels' counter layout");
 
 struct PpBufs {
   unsigned char* cls;    // per stored state: PC_*
@@ -963,22 +1102,6 @@ __global__ __launch_bounds__(LV_BLOCK) void k_pp_expand(LvBufs<R> B, PpBufs pp, 
   }
 }
 
-// the least stuck state of level order[a, b), as k_lv_pick
-template <typename R>
-__global__ __launch_bounds__(LV_BLOCK) void k_pp_pick(LvBufs<R> B, PpBufs pp, u64 a, u64 b, int phase) {
-  using W = typename R::word;
-  const u64 stride = (u64)gridDim.x * LV_BLOCK;
-  for (u64 i = a + (u64)blockIdx.x * LV_BLOCK + threadIdx.x; i < b; i += stride) {
-    const u64 g = pp.order[i];
-    if (!pp.stuck[g]) continue;
-    const W s = B.store[g];
-    const u64 hi = sizeof(W) == 8 ? 0 : (u64)((unsigned __int128)s >> 64), lo = (u64)s;
-    if (phase == 0) atomicMin(&pp.ctr->key_hi, (unsigned long long)hi);
-    else if (phase == 1) { if (hi == pp.ctr->key_hi) atomicMin(&pp.ctr->key_lo, (unsigned long long)lo); }
-    else if (hi == pp.ctr->key_hi && lo == pp.ctr->key_lo) pp.ctr->pick = g;
-  }
-}
-
 // Kahn peeling over G': the states of in-degree 0 (stored indices), or with
 // left = 1 the ones that kept an in-edge (positions in `order`: G' BFS order)
 __global__ __launch_bounds__(LV_BLOCK) void k_pp_zero(PpBufs pp, u64 n, u32* list, int left) {
@@ -1046,14 +1169,6 @@ __global__ __launch_bounds__(LV_BLOCK) void k_pp_peel(LvBufs<R> B, PpBufs pp, co
   if (lost) atomicOr(&pp.ctr->flags, (unsigned)LV_LOOKUP);
 }
 
-// the states at positions pos[0 .. n) of `order` (checked by the host to lie inside it)
-template <typename R>
-__global__ __launch_bounds__(LV_BLOCK) void k_pp_gather(LvBufs<R> B, PpBufs pp, const u32* pos, u64 n,
-                                                        typename R::word* out) {
-  const u64 stride = (u64)gridDim.x * LV_BLOCK;
-  for (u64 i = (u64)blockIdx.x * LV_BLOCK + threadIdx.x; i < n; i += stride) out[i] = B.store[pp.order[pos[i]]];
-}
-
 // The path inside G' from its root seed to stored state g, behind the reach
 // BFS path from Init to that seed; *seed_at = the seed's place in the trace
 template <typename R>
@@ -1083,6 +1198,29 @@ int pp_path(const LvBufs<R>& B, const PpBufs& pp, const R& hg, u64 g, LvTrace* t
   return 0;
 }
 
+// the property pass's G' is `order`: positions in it, in-degree by stored index
+template <typename R>
+struct PropView {
+  Reach<R>& r;
+  const R& hg;
+  const PpBufs& pp;
+  tlcg_property* out;
+  PpCtr* d_ctr;
+  PpCtr& h;
+  const u32* order;
+  u64 n_all;
+  const unsigned char* stuck;
+  void zero(u64 n, u32* list, int left) { k_pp_zero<<<r.grid(n), LV_BLOCK>>>(pp, n, list, left); }
+  void peel(const u32* list, u64 n, u32* next) { k_pp_peel<R><<<r.grid(n), LV_BLOCK>>>(r.B, pp, list, n, next); }
+  int path(u64 g, LvTrace* tr, std::string* err) { return pp_path(r.B, pp, hg, g, tr, &out->seed_at, err); }
+  // the first seed in the BFS order of the reachable states, then stuttering
+  int stutter(LvTrace* tr, std::string* err) {
+    if (const int rc = path_to(r.B, hg, h.first_seed, tr, err)) return rc;
+    out->seed_at = (int)tr->states.size() - 1;
+    return 0;
+  }
+};
+
 // dg / hg: the graph as the kernels / the host read it, cl: the classifier
 // (device memory behind it).  -7: P or Q failed to evaluate on stored state
 // out->error_state, *tr the BFS path to it.
@@ -1090,260 +1228,73 @@ template <typename G, typename C>
 int run_property(const G& dg0, const G& hg0, const C& cl, const tlcg_opts* o, int fair, int form, tlcg_property* out,
                  LvTrace* tr, std::string* err) {
   using R = ReachAll<G>;
-  using W = typename G::word;
   const R dg{dg0}, hg{hg0};
-  const unsigned grid_cap = lv_grid_cap();
-  auto grid_for = [grid_cap](u64 n) { return lv_grid(n, grid_cap); };
-  u64 cap = o && o->state_capacity ? o->state_capacity : (u64)1 << 22;
-  int log2 = o && o->log2_fpset_slots > 0 ? o->log2_fpset_slots : 0;
-  hipEvent_t e0, e1;
-  LV_CHECK(hipEventCreate(&e0));
-  LV_CHECK(hipEventCreate(&e1));
-  struct EvGuard {
-    hipEvent_t a, b;
-    ~EvGuard() {
-      hipEventDestroy(a);
-      hipEventDestroy(b);
-    }
-  } evg{e0, e1};
   tlcg_liveness* lv = &out->lv;
-  for (int attempt = 0;; ++attempt) {
-    if (cap >= (1ull << 32) - 1) {
-      *err = "the property check indexes states with 32 bits: more than 2^32 - 1 reachable states";
-      return -5;
-    }
-    int lg = log2;
-    if (lg <= 0 || attempt > 0) {
-      lg = 10;
-      while ((1ull << lg) < 2 * cap) ++lg;
-    }
-    if (lg > 32) lg = 32;
-    DevMem mem;
-    LvBufs<R> B;
-    B.g = dg;
-    B.log2 = lg;
-    B.cap = cap;
-    const u64 nslots = 1ull << lg;
-    PpBufs pp{};
-    // 1. reach (the peel lists and G' arrays are sized by the capacity, so that
-    // what does not fit is known before the BFS, not after it)
-    u32 *la = nullptr, *lb = nullptr;
-    if (!mem.alloc(&B.slots, nslots * (sizeof(W) / 8)) || !mem.alloc(&B.store, cap) || !mem.alloc(&B.parent, cap) ||
-        !mem.alloc(&B.slot_of, cap) || !mem.alloc(&B.gidx_of, nslots) || !mem.alloc(&B.indeg, nslots) ||
-        !mem.alloc(&B.stuck, cap) || !mem.alloc(&B.ctr, 1) || !mem.alloc(&pp.cls, cap) ||
-        !mem.alloc(&pp.member, cap / 32 + 1) || !mem.alloc(&pp.order, cap) || !mem.alloc(&pp.gparent, cap) ||
-        !mem.alloc(&la, cap) || !mem.alloc(&lb, cap) || !mem.alloc(&pp.ctr, 1)) {
-      if (cap > (1ull << 20) && attempt < 8) {
-        cap /= 2;
-        log2 = 0;
-        continue;
-      }
-      *err = "property: device allocation failed (" + std::to_string(cap) + " states, 2^" + std::to_string(lg) +
-             " FPSet slots)";
-      return -5;
-    }
-    LV_CHECK(hipMemset(B.slots, 0, nslots * sizeof(W)));
-    LV_CHECK(hipMemset(B.indeg, 0, nslots * sizeof(u32)));
-    LvCtr h{};
-    h.first_init = ~0ull;
-    LV_CHECK(hipMemcpy(B.ctr, &h, sizeof h, hipMemcpyHostToDevice));
-    auto read_ctr = [&]() -> int {
-      LV_CHECK(hipMemcpy(&h, B.ctr, sizeof h, hipMemcpyDeviceToHost));
-      return 0;
-    };
-    float ms_total = 0.f, ms = 0.f;
-    LV_CHECK(hipEventRecord(e0, 0));
-    k_lv_init<R><<<grid_for(hg.n_init()), LV_BLOCK>>>(B);
-    LV_CHECK(hipGetLastError());
-    if (read_ctr()) return -4;
-    std::vector<u64> level_base{0, std::min<u64>(h.n, cap)};
-    bool again = (h.flags & (LV_FPSET | LV_STORE)) != 0;
-    while (!again && level_base.back() > level_base[level_base.size() - 2]) {
-      const u64 a = level_base[level_base.size() - 2], b = level_base.back();
-      k_lv_expand<R><<<grid_for(b - a), LV_BLOCK>>>(B, a, b, fair);
-      LV_CHECK(hipGetLastError());
-      if (read_ctr()) return -4;
-      if (h.flags & LV_EVAL) {
-        *err = "property: an evaluation error while computing a successor (run the safety check first)";
-        return -6;
-      }
-      if ((again = (h.flags & (LV_FPSET | LV_STORE)) != 0)) break;
-      level_base.push_back(h.n);
-    }
-    LV_CHECK(hipEventRecord(e1, 0));
-    LV_CHECK(hipEventSynchronize(e1));
-    LV_CHECK(hipEventElapsedTime(&ms, e0, e1));
-    ms_total += ms;
-    if (again) {
-      cap *= 4;
-      continue;  // redo with a larger store and FPSet
-    }
-    const u64 n_all = h.n;
-    out->reachable = n_all;
-    // 2. classify
-    pp.indeg = B.indeg;  // (nslots >= n_all entries; by stored index from here on)
-    pp.stuck = B.stuck;
-    pp.n_all = n_all;
-    PpCtr c{};
-    c.first_seed = c.first_err = ~0ull;
-    LV_CHECK(hipMemcpy(pp.ctr, &c, sizeof c, hipMemcpyHostToDevice));
-    auto read_pp = [&]() -> int {
-      LV_CHECK(hipMemcpy(&c, pp.ctr, sizeof c, hipMemcpyDeviceToHost));
-      return 0;
-    };
-    LV_CHECK(hipMemset(pp.indeg, 0, n_all * sizeof(u32)));
-    LV_CHECK(hipMemset(pp.stuck, 0, n_all));
-    LV_CHECK(hipMemset(pp.member, 0, (n_all / 32 + 1) * sizeof(u32)));
-    LV_CHECK(hipEventRecord(e0, 0));
-    k_pp_classify<R, C><<<grid_for(n_all), LV_BLOCK>>>(B, cl, pp);
-    LV_CHECK(hipGetLastError());
-    LV_CHECK(hipEventRecord(e1, 0));
-    LV_CHECK(hipEventSynchronize(e1));
-    LV_CHECK(hipEventElapsedTime(&ms, e0, e1));
-    out->classify_ms = ms;
-    ms_total += ms;
-    if (read_pp()) return -4;
-    if (c.first_err != ~0ull) {
-      out->error_state = (int64_t)c.first_err;
-      lv->kernel_ms = ms_total;
-      if (const int rc = path_to(B, hg, c.first_err, tr, err)) return rc;
-      *err = "property: P or Q failed to evaluate on a reachable state";
-      return -7;
-    }
-    // 3. seed, 4. sub-BFS
-    LV_CHECK(hipEventRecord(e0, 0));
-    const u64 seed_range = form == TLCG_PROP_EVENTUALLY ? level_base[1] : n_all;
-    k_pp_seed<<<grid_for(seed_range), LV_BLOCK>>>(pp, seed_range, form);
-    LV_CHECK(hipGetLastError());
-    if (read_pp()) return -4;
-    out->seeds = c.n;
-    std::vector<u64> glevel{0, c.n}, level_stuck;
-    while (glevel.back() > glevel[glevel.size() - 2]) {
-      const u64 a = glevel[glevel.size() - 2], b = glevel.back();
-      LV_CHECK(hipMemset(&pp.ctr->stuck, 0, sizeof(unsigned long long)));
-      k_pp_expand<R><<<grid_for(b - a), LV_BLOCK>>>(B, pp, a, b, fair);
-      LV_CHECK(hipGetLastError());
-      if (read_pp()) return -4;
-      if (c.flags & (LV_EVAL | LV_LOOKUP)) {
-        *err = "property: a successor of a reachable state is missing from the FPSet";
-        return -6;
-      }
-      level_stuck.push_back(c.stuck);
-      glevel.push_back(c.n);
-    }
-    const u64 n = c.n;
-    lv->states_notp = n;
-    lv->init_notp = out->seeds;
-    lv->edges_notp = c.edges;
-    lv->depth = (int32_t)(glevel.size() - 2);
-    lv->stuck = 0;
-    for (u64 x : level_stuck) lv->stuck += x;
-    // 5. Kahn peeling
-    LV_CHECK(hipMemset(&pp.ctr->next, 0, sizeof(unsigned long long)));
-    k_pp_zero<<<grid_for(n), LV_BLOCK>>>(pp, n, la, 0);
-    LV_CHECK(hipGetLastError());
-    if (read_pp()) return -4;
-    u64 removed = 0, cur = c.next;
-    int rounds = 0;
-    while (cur) {
-      removed += cur;
-      ++rounds;
-      LV_CHECK(hipMemset(&pp.ctr->next, 0, sizeof(unsigned long long)));
-      k_pp_peel<R><<<grid_for(cur), LV_BLOCK>>>(B, pp, la, cur, lb);
-      LV_CHECK(hipGetLastError());
-      if (read_pp()) return -4;
-      if (c.flags & LV_LOOKUP) {
-        *err = "property: a successor in G' is missing from the FPSet";
-        return -6;
-      }
-      cur = c.next;
-      std::swap(la, lb);
-    }
-    LV_CHECK(hipEventRecord(e1, 0));
-    LV_CHECK(hipEventSynchronize(e1));
-    LV_CHECK(hipEventElapsedTime(&ms, e0, e1));
-    ms_total += ms;
-    lv->peel_rounds = rounds;
-    lv->on_cycles = n - removed;
-    lv->kernel_ms = ms_total;
-    // 6. verdict and counterexample
-    if (lv->stuck && fair == TLCG_FAIR_NONE) {
-      // every state of G' may stutter forever: the first seed in the BFS order
-      // of the reachable states, then stuttering
-      lv->holds = 0;
-      lv->kind = TLCG_LIVE_STUTTERING;
-      if (const int rc = path_to(B, hg, c.first_seed, tr, err)) return rc;
-      out->seed_at = (int)tr->states.size() - 1;
-      return 0;
-    }
-    if (lv->stuck) {
-      lv->holds = 0;
-      lv->kind = TLCG_LIVE_STUTTERING;
-      size_t l = 0;
-      while (level_stuck[l] == 0) ++l;
-      const u64 a = glevel[l], b = glevel[l + 1];
-      c.key_hi = c.key_lo = ~0ull;
-      c.pick = ~0ull;
-      LV_CHECK(hipMemcpy(pp.ctr, &c, sizeof c, hipMemcpyHostToDevice));
-      for (int ph = 0; ph < 3; ++ph) k_pp_pick<R><<<grid_for(b - a), LV_BLOCK>>>(B, pp, a, b, ph);
-      LV_CHECK(hipGetLastError());
-      if (read_pp()) return -4;
-      if (c.pick >= n_all) {
-        *err = "property: no stuck state found in its level";
-        return -6;
-      }
-      return pp_path(B, pp, hg, c.pick, tr, &out->seed_at, err);
-    }
-    if (removed == n) {
-      lv->holds = 1;
-      lv->kind = TLCG_LIVE_HOLDS;
-      return 0;
-    }
-    // a cycle: the states left after peeling, by their place in G' BFS order
-    lv->holds = 0;
-    lv->kind = TLCG_LIVE_CYCLE;
-    const u64 left = n - removed;
-    if (left > (1ull << 26)) {
-      *err = "property: " + std::to_string(left) + " states lie on or after cycles; the lasso extraction takes at most 2^26";
-      return -5;
-    }
-    LV_CHECK(hipMemset(&pp.ctr->next, 0, sizeof(unsigned long long)));
-    k_pp_zero<<<grid_for(n), LV_BLOCK>>>(pp, n, la, 1);
-    LV_CHECK(hipGetLastError());
-    std::vector<u32> pos(left), ord_h(n);
-    std::vector<W> st(left);
-    LV_CHECK(hipMemcpy(pos.data(), la, left * sizeof(u32), hipMemcpyDeviceToHost));
-    LV_CHECK(hipMemcpy(ord_h.data(), pp.order, n * sizeof(u32), hipMemcpyDeviceToHost));
-    std::sort(pos.begin(), pos.end());
-    for (u64 i = 0; i < left; ++i)
-      if (pos[i] >= n || ord_h[pos[i]] >= n_all) {
-        *err = "property: a state left after peeling lies outside G'";
-        return -6;
-      }
-    // their states, gathered on the device in that order and copied at once
-    W* d_st = nullptr;
-    if (!mem.alloc(&d_st, left)) {
-      *err = "property: device allocation failed (the states left after peeling)";
-      return -5;
-    }
-    LV_CHECK(hipMemcpy(la, pos.data(), left * sizeof(u32), hipMemcpyHostToDevice));
-    k_pp_gather<R><<<grid_for(left), LV_BLOCK>>>(B, pp, la, left, d_st);
-    LV_CHECK(hipGetLastError());
-    LV_CHECK(hipMemcpy(st.data(), d_st, left * sizeof(W), hipMemcpyDeviceToHost));
-    // (the walk stays among the states left, none of which satisfies Q, so the
-    // host graph needs no Q of its own)
-    u64 p_entry = 0;
-    std::vector<u128> cyc;
-    std::vector<int> cyc_act;
-    int back = -1;
-    if (lasso_walk(hg, st, pos, &p_entry, &cyc, &cyc_act, &back, err) != 0) return -6;
-    if (const int rc = pp_path(B, pp, hg, ord_h[p_entry], tr, &out->seed_at, err)) return rc;
-    tr->loop_to = (int)tr->states.size() - 1;
-    tr->states.insert(tr->states.end(), cyc.begin(), cyc.end());
-    tr->actions.insert(tr->actions.end(), cyc_act.begin(), cyc_act.end());
-    tr->back_action = back;
-    return 0;
+  // 1. reach (the peel lists and G' arrays are sized by the capacity, so that
+  // what does not fit is known before the BFS, not after it)
+  Reach<R> r;
+  PpBufs pp{};
+  u32 *la = nullptr, *lb = nullptr;
+  auto extra = [&](DevMem& mem, u64 cap) {
+    return mem.alloc(&pp.cls, cap) && mem.alloc(&pp.member, cap / 32 + 1) && mem.alloc(&pp.order, cap) &&
+           mem.alloc(&pp.gparent, cap) && mem.alloc(&la, cap) && mem.alloc(&lb, cap) && mem.alloc(&pp.ctr, 1);
+  };
+  if (const int rc = r.run(dg, o, fair, NM_PROPERTY, extra, err)) return rc;
+  const LvBufs<R>& B = r.B;
+  const u64 n_all = r.h.n;
+  out->reachable = n_all;
+  // 2. classify
+  pp.indeg = B.indeg;  // (nslots >= n_all entries; by stored index from here on)
+  pp.stuck = B.stuck;
+  pp.n_all = n_all;
+  PpCtr c{};
+  c.first_seed = c.first_err = ~0ull;
+  LV_CHECK(hipMemcpy(pp.ctr, &c, sizeof c, hipMemcpyHostToDevice));
+  LV_CHECK(hipMemset(pp.indeg, 0, n_all * sizeof(u32)));
+  LV_CHECK(hipMemset(pp.stuck, 0, n_all));
+  LV_CHECK(hipMemset(pp.member, 0, (n_all / 32 + 1) * sizeof(u32)));
+  LV_CHECK(r.tm.start());
+  k_pp_classify<R, C><<<r.grid(n_all), LV_BLOCK>>>(B, cl, pp);
+  LV_CHECK(hipGetLastError());
+  float ms = 0.f;
+  LV_CHECK(r.tm.stop(&ms));
+  out->classify_ms = ms;
+  const float ms_before = r.ms + ms;
+  if (read_ctr(&c, pp.ctr, err)) return -4;
+  if (c.first_err != ~0ull) {
+    out->error_state = (int64_t)c.first_err;
+    lv->kernel_ms = ms_before;
+    if (const int rc = path_to(B, hg, c.first_err, tr, err)) return rc;
+    *err = "property: P or Q failed to evaluate on a reachable state";
+    return -7;
   }
+  // 3. seed, 4. sub-BFS
+  LV_CHECK(r.tm.start());
+  const u64 seed_range = form == TLCG_PROP_EVENTUALLY ? r.level_base[1] : n_all;
+  k_pp_seed<<<r.grid(seed_range), LV_BLOCK>>>(pp, seed_range, form);
+  LV_CHECK(hipGetLastError());
+  if (read_ctr(&c, pp.ctr, err)) return -4;
+  out->seeds = c.n;
+  std::vector<u64> glevel{0, c.n}, level_stuck;
+  while (glevel.back() > glevel[glevel.size() - 2]) {
+    const u64 a = glevel[glevel.size() - 2], b = glevel.back(), stuck_before = c.stuck;
+    k_pp_expand<R><<<r.grid(b - a), LV_BLOCK>>>(B, pp, a, b, fair);
+    LV_CHECK(hipGetLastError());
+    if (read_ctr(&c, pp.ctr, err)) return -4;
+    if (c.flags & (LV_EVAL | LV_LOOKUP)) {
+      *err = "property: a successor of a reachable state is missing from the FPSet";
+      return -6;
+    }
+    level_stuck.push_back(c.stuck - stuck_before);
+    glevel.push_back(c.n);
+  }
+  lv->states_notp = c.n;
+  lv->init_notp = out->seeds;
+  lv->edges_notp = c.edges;
+  lv->depth = (int32_t)(glevel.size() - 2);
+  // 5. Kahn peeling, 6. verdict and counterexample
+  PropView<R> v{r, hg, pp, out, pp.ctr, c, pp.order, n_all, pp.stuck};
+  return peel_verdict(v, hg, fair, glevel, level_stuck, la, lb, ms_before, NM_PROPERTY, lv, tr, err);
 }
 
 }  // namespace
@@ -1351,10 +1302,7 @@ int run_property(const G& dg0, const G& hg0, const C& cl, const tlcg_opts* o, in
 extern "C" int tlcg_check_termination(const tlcg_model* m, const tlcg_opts* o, int32_t fairness, tlcg_liveness* out,
                                       uint64_t* states, int32_t* actions, int32_t cap, int32_t* len, char* err,
                                       int32_t err_cap) {
-  auto fail = [&](int rc, const std::string& e) {
-    if (err && err_cap > 0) std::snprintf(err, (size_t)err_cap, "%s", e.c_str());
-    return rc;
-  };
+  const Fail fail{err, err_cap};
   if (!m || !out) return fail(-1, "null argument");
   if (fairness != TLCG_FAIR_NONE && fairness != TLCG_FAIR_WF_NEXT) return fail(-1, "unknown fairness");
   std::memset(out, 0, sizeof *out);
@@ -1379,10 +1327,7 @@ extern "C" int tlcg_liveness_graph_selftest(const uint32_t* row, const uint32_t*
                                             uint32_t n_init, int32_t words, const tlcg_opts* o, int32_t fairness,
                                             tlcg_liveness* out, uint64_t* states, int32_t* actions, int32_t cap,
                                             int32_t* len, char* err, int32_t err_cap) {
-  auto fail = [&](int rc, const std::string& e) {
-    if (err && err_cap > 0) std::snprintf(err, (size_t)err_cap, "%s", e.c_str());
-    return rc;
-  };
+  const Fail fail{err, err_cap};
   if (!row || !out || (n && !is_p)) return fail(-1, "null argument");
   if (fairness != TLCG_FAIR_NONE && fairness != TLCG_FAIR_WF_NEXT) return fail(-1, "unknown fairness");
   if (words != 1 && words != 2) return fail(-1, "words must be 1 or 2");
@@ -1391,10 +1336,7 @@ extern "C" int tlcg_liveness_graph_selftest(const uint32_t* row, const uint32_t*
   out->fairness = fairness;
   if (len) *len = 0;
   std::string e;
-  {  // a malformed graph is refused before the device is touched
-    ExplicitGraph<u64> shape{};
-    if (!explicit_graph_shape(row, col, n, n_init, &shape, &e)) return fail(-1, e);
-  }
+  if (!graph_ok(row, col, n, n_init, &e)) return fail(-1, e);
   if (hipSetDevice(o ? o->device : 0) != hipSuccess) return fail(-4, "hipSetDevice failed");
   const auto t0 = std::chrono::steady_clock::now();
   LvTrace tr;
@@ -1408,17 +1350,10 @@ extern "C" int tlcg_liveness_graph_selftest(const uint32_t* row, const uint32_t*
 
 namespace {
 
-void pp_copy_out(const LvTrace& tr, int words, tlcg_property* out, uint64_t* states, int32_t* actions, int32_t cap,
-                 int32_t* len) {
-  lv_copy_out(tr, words, &out->lv, states, actions, cap, len);
-}
-
 template <typename W>
 int run_model_property(const HostModel& hm, const UserProg* d_prog, const tlcg_opts* o, int fair, int form,
                        tlcg_property* out, LvTrace* tr, std::string* err) {
-  ModelGraph<W> g;
-  g.L = hm.L;
-  g.n_init_ = hm.n_init;
+  const ModelGraph<W> g{hm.L, hm.n_init};
   const ProgClass<W> cl{hm.L, d_prog};
   return run_property(g, g, cl, o, fair, form, out, tr, err);
 }
@@ -1427,27 +1362,13 @@ template <typename W>
 int run_explicit_property(const uint32_t* row, const uint32_t* col, const uint8_t* is_p, const uint8_t* is_q,
                           uint32_t n, uint32_t n_init, const tlcg_opts* o, int fair, int form, tlcg_property* out,
                           LvTrace* tr, std::string* err) {
-  ExplicitGraph<W> hg{};
-  if (!explicit_graph_shape(row, col, n, n_init, &hg, err)) return -1;
-  hg.row = row;
-  hg.col = col;
-  hg.p = nullptr;  // (ReachAll asks for no P)
   DevMem mem;
-  uint32_t *d_row = nullptr, *d_col = nullptr;
-  unsigned char *d_p = nullptr, *d_q = nullptr;
-  if (!mem.alloc(&d_row, (u64)n + 1) || !mem.alloc(&d_col, row[n]) || !mem.alloc(&d_p, n) || !mem.alloc(&d_q, n)) {
-    *err = "graph: device allocation failed";
-    return -5;
-  }
-  LV_CHECK(hipMemcpy(d_row, row, ((size_t)n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
-  if (row[n]) LV_CHECK(hipMemcpy(d_col, col, (size_t)row[n] * sizeof(uint32_t), hipMemcpyHostToDevice));
-  const bool has_p = form == TLCG_PROP_LEADS_TO;
-  if (n && has_p) LV_CHECK(hipMemcpy(d_p, is_p, n, hipMemcpyHostToDevice));
-  if (n) LV_CHECK(hipMemcpy(d_q, is_q, n, hipMemcpyHostToDevice));
-  ExplicitGraph<W> dg = hg;
-  dg.row = d_row;
-  dg.col = d_col;
-  const ByteClass<W> cl{has_p ? d_p : nullptr, d_q};
+  ExplicitGraph<W> hg, dg;  // (without a P: ReachAll asks for none)
+  if (const int rc = upload_graph(row, col, n, n_init, mem, &hg, &dg, err)) return rc;
+  ByteClass<W> cl{nullptr, nullptr};
+  if (form == TLCG_PROP_LEADS_TO)
+    if (const int rc = upload(mem, is_p, n, &cl.p, err)) return rc;
+  if (const int rc = upload(mem, is_q, n, &cl.q, err)) return rc;
   return run_property(dg, hg, cl, o, fair, form, out, tr, err);
 }
 
@@ -1465,10 +1386,7 @@ void pp_reset(tlcg_property* out, int fairness, int form) {
 extern "C" int tlcg_check_property(const tlcg_model* m, const tlcg_opts* o, int32_t fairness, const char* name,
                                    tlcg_property* out, uint64_t* states, int32_t* actions, int32_t cap, int32_t* len,
                                    char* err, int32_t err_cap) {
-  auto fail = [&](int rc, const std::string& e) {
-    if (err && err_cap > 0) std::snprintf(err, (size_t)err_cap, "%s", e.c_str());
-    return rc;
-  };
+  const Fail fail{err, err_cap};
   if (!m || !out || !name) return fail(-1, "null argument");
   if (fairness != TLCG_FAIR_NONE && fairness != TLCG_FAIR_WF_NEXT) return fail(-1, "unknown fairness");
   pp_reset(out, fairness, 0);
@@ -1498,11 +1416,11 @@ extern "C" int tlcg_check_property(const tlcg_model* m, const tlcg_opts* o, int3
     const bool p_err = eval_user<u128>(hm.L, *prog, 0, s) == EV_ERROR;
     e = std::string("evaluating ") + (p_err ? "P (the left operand)" : "Q") + " of property " + name +
         " failed on a reachable state (the last state of the trace)";
-    pp_copy_out(tr, words, out, states, actions, cap, len);
+    lv_copy_out(tr, words, &out->lv, states, actions, cap, len);
     return fail(rc, e);
   }
   if (rc) return fail(rc, e);
-  pp_copy_out(tr, words, out, states, actions, cap, len);
+  lv_copy_out(tr, words, &out->lv, states, actions, cap, len);
   return 0;
 }
 
@@ -1511,10 +1429,7 @@ extern "C" int tlcg_property_graph_selftest(const uint32_t* row, const uint32_t*
                                             const tlcg_opts* o, int32_t fairness, int32_t form, tlcg_property* out,
                                             uint64_t* states, int32_t* actions, int32_t cap, int32_t* len, char* err,
                                             int32_t err_cap) {
-  auto fail = [&](int rc, const std::string& e) {
-    if (err && err_cap > 0) std::snprintf(err, (size_t)err_cap, "%s", e.c_str());
-    return rc;
-  };
+  const Fail fail{err, err_cap};
   if (form != TLCG_PROP_EVENTUALLY && form != TLCG_PROP_INFINITELY_OFTEN && form != TLCG_PROP_LEADS_TO)
     return fail(-1, "unknown form");
   if (!row || !out || (n && (!is_q || (form == TLCG_PROP_LEADS_TO && !is_p)))) return fail(-1, "null argument");
@@ -1524,10 +1439,7 @@ extern "C" int tlcg_property_graph_selftest(const uint32_t* row, const uint32_t*
   pp_reset(out, fairness, form);
   if (len) *len = 0;
   std::string e;
-  {  // a malformed graph is refused before the device is touched
-    ExplicitGraph<u64> shape{};
-    if (!explicit_graph_shape(row, col, n, n_init, &shape, &e)) return fail(-1, e);
-  }
+  if (!graph_ok(row, col, n, n_init, &e)) return fail(-1, e);
   if (hipSetDevice(o ? o->device : 0) != hipSuccess) return fail(-4, "hipSetDevice failed");
   const auto t0 = std::chrono::steady_clock::now();
   LvTrace tr;
@@ -1536,7 +1448,7 @@ extern "C" int tlcg_property_graph_selftest(const uint32_t* row, const uint32_t*
                      : run_explicit_property<u128>(row, col, is_p, is_q, n, n_init, o, fairness, form, out, &tr, &e);
   out->lv.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (rc) return fail(rc, e);
-  pp_copy_out(tr, words, out, states, actions, cap, len);
+  lv_copy_out(tr, words, &out->lv, states, actions, cap, len);
   return 0;
 }
 
@@ -1635,152 +1547,73 @@ int run_action(const G& dg0, const G& hg0, const E& dev, const E& host, const tl
   using R = ReachAll<G>;
   using W = typename G::word;
   const R dg{dg0}, hg{hg0};
-  const unsigned grid_cap = lv_grid_cap();
-  auto grid_for = [grid_cap](u64 n) { return lv_grid(n, grid_cap); };
-  u64 cap = o && o->state_capacity ? o->state_capacity : (u64)1 << 22;
-  int log2 = o && o->log2_fpset_slots > 0 ? o->log2_fpset_slots : 0;
-  hipEvent_t e0, e1;
-  LV_CHECK(hipEventCreate(&e0));
-  LV_CHECK(hipEventCreate(&e1));
-  struct EvGuard {
-    hipEvent_t a, b;
-    ~EvGuard() {
-      hipEventDestroy(a);
-      hipEventDestroy(b);
-    }
-  } evg{e0, e1};
-  for (int attempt = 0;; ++attempt) {
-    if (cap >= (1ull << 32) - 1) {
-      *err = "the action property check indexes states with 32 bits: more than 2^32 - 1 reachable states";
-      return -5;
-    }
-    int lg = log2;
-    if (lg <= 0 || attempt > 0) {
-      lg = 10;
-      while ((1ull << lg) < 2 * cap) ++lg;
-    }
-    if (lg > 32) lg = 32;
-    DevMem mem;
-    LvBufs<R> B;
-    B.g = dg;
-    B.log2 = lg;
-    B.cap = cap;
-    const u64 nslots = 1ull << lg;
-    ApCtr* d_ctr = nullptr;
-    // 1. reach
-    if (!mem.alloc(&B.slots, nslots * (sizeof(W) / 8)) || !mem.alloc(&B.store, cap) || !mem.alloc(&B.parent, cap) ||
-        !mem.alloc(&B.slot_of, cap) || !mem.alloc(&B.gidx_of, nslots) || !mem.alloc(&B.indeg, nslots) ||
-        !mem.alloc(&B.stuck, cap) || !mem.alloc(&B.ctr, 1) || !mem.alloc(&d_ctr, 1)) {
-      if (cap > (1ull << 20) && attempt < 8) {
-        cap /= 2;
-        log2 = 0;
-        continue;
-      }
-      *err = "action property: device allocation failed (" + std::to_string(cap) + " states, 2^" +
-             std::to_string(lg) + " FPSet slots)";
-      return -5;
-    }
-    LV_CHECK(hipMemset(B.slots, 0, nslots * sizeof(W)));
-    LV_CHECK(hipMemset(B.indeg, 0, nslots * sizeof(u32)));
-    LvCtr h{};
-    h.first_init = ~0ull;
-    LV_CHECK(hipMemcpy(B.ctr, &h, sizeof h, hipMemcpyHostToDevice));
-    auto read_ctr = [&]() -> int {
-      LV_CHECK(hipMemcpy(&h, B.ctr, sizeof h, hipMemcpyDeviceToHost));
-      return 0;
-    };
-    float ms = 0.f;
-    LV_CHECK(hipEventRecord(e0, 0));
-    k_lv_init<R><<<grid_for(hg.n_init()), LV_BLOCK>>>(B);
-    LV_CHECK(hipGetLastError());
-    if (read_ctr()) return -4;
-    std::vector<u64> level_base{0, std::min<u64>(h.n, cap)};
-    bool again = (h.flags & (LV_FPSET | LV_STORE)) != 0;
-    while (!again && level_base.back() > level_base[level_base.size() - 2]) {
-      const u64 a = level_base[level_base.size() - 2], b = level_base.back();
-      k_lv_expand<R><<<grid_for(b - a), LV_BLOCK>>>(B, a, b, TLCG_FAIR_WF_NEXT);
-      LV_CHECK(hipGetLastError());
-      if (read_ctr()) return -4;
-      if (h.flags & LV_EVAL) {
-        *err = "action property: an evaluation error while computing a successor (run the safety check first)";
-        return -6;
-      }
-      if ((again = (h.flags & (LV_FPSET | LV_STORE)) != 0)) break;
-      level_base.push_back(h.n);
-    }
-    LV_CHECK(hipEventRecord(e1, 0));
-    LV_CHECK(hipEventSynchronize(e1));
-    LV_CHECK(hipEventElapsedTime(&ms, e0, e1));
-    if (again) {
-      cap *= 4;
-      continue;  // redo with a larger store and FPSet
-    }
-    const u64 n = h.n;
-    out->reachable = n;
-    out->depth = (int32_t)(level_base.size() - 2);
-    out->kernel_ms = ms;
-    // 2. check
-    ApCtr c{};
-    c.first = ~0ull;
-    LV_CHECK(hipMemcpy(d_ctr, &c, sizeof c, hipMemcpyHostToDevice));
-    LV_CHECK(hipEventRecord(e0, 0));
-    k_ap_check<R, E><<<grid_for(n), LV_BLOCK>>>(B, dev, n, d_ctr);
-    LV_CHECK(hipGetLastError());
-    LV_CHECK(hipEventRecord(e1, 0));
-    LV_CHECK(hipEventSynchronize(e1));
-    LV_CHECK(hipEventElapsedTime(&ms, e0, e1));
-    LV_CHECK(hipMemcpy(&c, d_ctr, sizeof c, hipMemcpyDeviceToHost));
-    out->check_ms = ms;
-    out->kernel_ms += ms;
-    out->steps = c.steps;
-    out->violating = c.violating;
-    out->erroring = c.erroring;
-    if (c.first == ~0ull) {
-      out->holds = 1;
-      return 0;
-    }
-    // 3. the reported step
-    out->holds = 0;
-    if (c.first >= n) {
-      *err = "action property: the first flagged state lies outside the store";
-      return -6;
-    }
-    size_t lv = 0;
-    while (level_base[lv + 1] <= c.first) ++lv;
-    const u64 a = level_base[lv], b = level_base[lv + 1];
-    h.key_hi = h.key_lo = ~0ull;
-    h.pick = ~0ull;
-    LV_CHECK(hipMemcpy(B.ctr, &h, sizeof h, hipMemcpyHostToDevice));
-    for (int ph = 0; ph < 3; ++ph) k_lv_pick<R><<<grid_for(b - a), LV_BLOCK>>>(B, a, b, ph);
-    LV_CHECK(hipGetLastError());
-    if (read_ctr()) return -4;
-    if (h.pick < a || h.pick >= b) {
-      *err = "action property: no flagged state found in its level";
-      return -6;
-    }
-    W s;
-    LV_CHECK(hipMemcpy(&s, B.store + h.pick, sizeof(W), hipMemcpyDeviceToHost));
-    const int kmax = hg.moves_bound();
-    for (int k = 0; k < kmax; ++k) {
-      W t = 0;
-      int ord = 0;
-      if (hg.move(s, k, &t, &ord) != 1) continue;
-      const int v = host.verdict(s, k, t);
-      if (v == 0) continue;
-      out->step_depth = (int32_t)lv + 1;  // (levels count from 1, as depth does: Init is level 1)
-      out->step_action = hg.action_of(ord);
-      if (const int rc = path_to(B, hg, h.pick, tr, err)) return rc;
-      tr->states.push_back((u128)t);
-      tr->actions.push_back(out->step_action);
-      if (v != 1) {
-        out->error_state = (int64_t)h.pick;
-        return -7;
-      }
-      return 0;
-    }
-    *err = "action property: the host finds no violating step of the state the device flagged";
+  // 1. reach
+  Reach<R> r;
+  ApCtr* d_ctr = nullptr;
+  if (const int rc = r.run(dg, o, TLCG_FAIR_WF_NEXT, NM_ACTION,
+                           [&](DevMem& mem, u64) { return mem.alloc(&d_ctr, 1); }, err))
+    return rc;
+  const LvBufs<R>& B = r.B;
+  const u64 n = r.h.n;
+  out->reachable = n;
+  out->depth = (int32_t)(r.level_base.size() - 2);
+  // 2. check
+  ApCtr c{};
+  c.first = ~0ull;
+  LV_CHECK(hipMemcpy(d_ctr, &c, sizeof c, hipMemcpyHostToDevice));
+  LV_CHECK(r.tm.start());
+  k_ap_check<R, E><<<r.grid(n), LV_BLOCK>>>(B, dev, n, d_ctr);
+  LV_CHECK(hipGetLastError());
+  float ms = 0.f;
+  LV_CHECK(r.tm.stop(&ms));
+  LV_CHECK(hipMemcpy(&c, d_ctr, sizeof c, hipMemcpyDeviceToHost));
+  out->check_ms = ms;
+  out->kernel_ms = (double)r.ms + ms;
+  out->steps = c.steps;
+  out->violating = c.violating;
+  out->erroring = c.erroring;
+  if (c.first == ~0ull) {
+    out->holds = 1;
+    return 0;
+  }
+  // 3. the reported step
+  out->holds = 0;
+  if (c.first >= n) {
+    *err = "action property: the first flagged state lies outside the store";
     return -6;
   }
+  size_t lv = 0;
+  while (r.level_base[lv + 1] <= c.first) ++lv;
+  const u64 a = r.level_base[lv], b = r.level_base[lv + 1];
+  if (const int rc = pick_least(B.store, (const u32*)nullptr, B.stuck, B.ctr, &r.h, a, b, r.grid(b - a), err))
+    return rc;
+  const u64 pick = r.h.pick;
+  if (pick < a || pick >= b) {
+    *err = "action property: no flagged state found in its level";
+    return -6;
+  }
+  W s;
+  LV_CHECK(hipMemcpy(&s, B.store + pick, sizeof(W), hipMemcpyDeviceToHost));
+  const int kmax = hg.moves_bound();
+  for (int k = 0; k < kmax; ++k) {
+    W t = 0;
+    int ord = 0;
+    if (hg.move(s, k, &t, &ord) != 1) continue;
+    const int v = host.verdict(s, k, t);
+    if (v == 0) continue;
+    out->step_depth = (int32_t)lv + 1;  // (levels count from 1, as depth does: Init is level 1)
+    out->step_action = hg.action_of(ord);
+    if (const int rc = path_to(B, hg, pick, tr, err)) return rc;
+    tr->states.push_back((u128)t);
+    tr->actions.push_back(out->step_action);
+    if (v != 1) {
+      out->error_state = (int64_t)pick;
+      return -7;
+    }
+    return 0;
+  }
+  *err = "action property: the host finds no violating step of the state the device flagged";
+  return -6;
 }
 
 void ap_reset(tlcg_action_property* out) {
@@ -1789,50 +1622,22 @@ void ap_reset(tlcg_action_property* out) {
   out->error_state = -1;
 }
 
-void ap_copy_out(const LvTrace& tr, int words, tlcg_action_property* out, uint64_t* states, int32_t* actions,
-                 int32_t cap, int32_t* len) {
-  out->trace_len = (int32_t)tr.states.size();
-  if (states && actions && len) {
-    const int32_t n = std::min<int32_t>(cap, out->trace_len);
-    for (int32_t i = 0; i < n; ++i) {
-      split_words(tr.states[i], states + (size_t)i * words, words);
-      actions[i] = tr.actions[i];
-    }
-    *len = n;
-  }
-}
-
 template <typename W>
 int run_model_action(const HostModel& hm, const UserProg* h_prog, const UserProg* d_prog, const tlcg_opts* o,
                      tlcg_action_property* out, LvTrace* tr, std::string* err) {
-  ModelGraph<W> g;
-  g.L = hm.L;
-  g.n_init_ = hm.n_init;
+  const ModelGraph<W> g{hm.L, hm.n_init};
   return run_action(g, g, ProgStep<W>{hm.L, d_prog}, ProgStep<W>{hm.L, h_prog}, o, out, tr, err);
 }
 
 template <typename W>
 int run_explicit_action(const uint32_t* row, const uint32_t* col, const uint8_t* verdict, uint32_t n, uint32_t n_init,
                         const tlcg_opts* o, tlcg_action_property* out, LvTrace* tr, std::string* err) {
-  ExplicitGraph<W> hg{};
-  if (!explicit_graph_shape(row, col, n, n_init, &hg, err)) return -1;
-  hg.row = row;
-  hg.col = col;
-  hg.p = nullptr;  // (ReachAll asks for no P)
   DevMem mem;
-  uint32_t *d_row = nullptr, *d_col = nullptr;
-  unsigned char* d_v = nullptr;
-  if (!mem.alloc(&d_row, (u64)n + 1) || !mem.alloc(&d_col, row[n]) || !mem.alloc(&d_v, row[n])) {
-    *err = "graph: device allocation failed";
-    return -5;
-  }
-  LV_CHECK(hipMemcpy(d_row, row, ((size_t)n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
-  if (row[n]) LV_CHECK(hipMemcpy(d_col, col, (size_t)row[n] * sizeof(uint32_t), hipMemcpyHostToDevice));
-  if (row[n]) LV_CHECK(hipMemcpy(d_v, verdict, row[n], hipMemcpyHostToDevice));
-  ExplicitGraph<W> dg = hg;
-  dg.row = d_row;
-  dg.col = d_col;
-  return run_action(dg, hg, ByteStep<W>{d_row, d_v}, ByteStep<W>{row, verdict}, o, out, tr, err);
+  ExplicitGraph<W> hg, dg;  // (without a P: ReachAll asks for none)
+  if (const int rc = upload_graph(row, col, n, n_init, mem, &hg, &dg, err)) return rc;
+  ByteStep<W> dev{dg.row, nullptr};
+  if (const int rc = upload(mem, verdict, row[n], &dev.v, err)) return rc;
+  return run_action(dg, hg, dev, ByteStep<W>{row, verdict}, o, out, tr, err);
 }
 
 // tlcg_action_eval_selftest: the program on pair i, one lane each
@@ -1856,10 +1661,7 @@ __global__ __launch_bounds__(LV_BLOCK) void k_ap_eval(Layout L, const UserProg* 
 extern "C" int tlcg_check_action_property(const tlcg_model* m, const tlcg_opts* o, const char* name,
                                           tlcg_action_property* out, uint64_t* states, int32_t* actions, int32_t cap,
                                           int32_t* len, char* err, int32_t err_cap) {
-  auto fail = [&](int rc, const std::string& e) {
-    if (err && err_cap > 0) std::snprintf(err, (size_t)err_cap, "%s", e.c_str());
-    return rc;
-  };
+  const Fail fail{err, err_cap};
   if (!m || !out || !name) return fail(-1, "null argument");
   ap_reset(out);
   if (len) *len = 0;
@@ -1885,7 +1687,7 @@ extern "C" int tlcg_check_action_property(const tlcg_model* m, const tlcg_opts* 
         " failed on a step of a reachable state (the last two states of the trace)";
   else if (rc)
     return fail(rc, e);
-  ap_copy_out(tr, words, out, states, actions, cap, len);
+  out->trace_len = trace_copy_out(tr, words, states, actions, cap, len);
   return rc ? fail(rc, e) : 0;
 }
 
@@ -1893,20 +1695,14 @@ extern "C" int tlcg_action_property_graph_selftest(const uint32_t* row, const ui
                                                    uint32_t n, uint32_t n_init, int32_t words, const tlcg_opts* o,
                                                    tlcg_action_property* out, uint64_t* states, int32_t* actions,
                                                    int32_t cap, int32_t* len, char* err, int32_t err_cap) {
-  auto fail = [&](int rc, const std::string& e) {
-    if (err && err_cap > 0) std::snprintf(err, (size_t)err_cap, "%s", e.c_str());
-    return rc;
-  };
+  const Fail fail{err, err_cap};
   if (!row || !out) return fail(-1, "null argument");
   if (words != 1 && words != 2) return fail(-1, "words must be 1 or 2");
   if (row[n] && (!col || !verdict)) return fail(-1, "null argument");
   ap_reset(out);
   if (len) *len = 0;
   std::string e;
-  {  // a malformed graph is refused before the device is touched
-    ExplicitGraph<u64> shape{};
-    if (!explicit_graph_shape(row, col, n, n_init, &shape, &e)) return fail(-1, e);
-  }
+  if (!graph_ok(row, col, n, n_init, &e)) return fail(-1, e);
   if (hipSetDevice(o ? o->device : 0) != hipSuccess) return fail(-4, "hipSetDevice failed");
   const auto t0 = std::chrono::steady_clock::now();
   LvTrace tr;
@@ -1915,16 +1711,13 @@ extern "C" int tlcg_action_property_graph_selftest(const uint32_t* row, const ui
   out->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (rc == -7) rc = 0;  // (error_state says so)
   if (rc) return fail(rc, e);
-  ap_copy_out(tr, words, out, states, actions, cap, len);
+  out->trace_len = trace_copy_out(tr, words, states, actions, cap, len);
   return 0;
 }
 
 extern "C" int tlcg_action_eval_selftest(const tlcg_model* m, const tlcg_opts* o, const char* name,
                                          const uint64_t* pairs, uint64_t n, uint8_t* out, char* err, int32_t cap) {
-  auto fail = [&](int rc, const std::string& e) {
-    if (err && cap > 0) std::snprintf(err, (size_t)cap, "%s", e.c_str());
-    return rc;
-  };
+  const Fail fail{err, cap};
   if (!m || !name || (n && (!pairs || !out))) return fail(-1, "null argument");
   HostModel hm;
   std::string e;

@@ -2,7 +2,7 @@
 tlcg_liveness_graph_selftest, against the plain reference of
 tests/liveness_ref.py.  The spec's own G' is acyclic for every cfg, so only
 graphs the test supplies reach the cycle verdict, the copy-out of the states
-left after peeling (k_lv_left), the lasso extraction and loop_to /
+left after peeling (k_lv_zero with left = 1, k_lv_gather), the lasso extraction and loop_to /
 back_action, and only they tell an exact Kahn peeling (peel_rounds,
 on_cycles, in-degrees with repeated edges) from one that merely ends empty.
 
