@@ -313,6 +313,14 @@ int64_t tlcg_host_lane_inv_selfcheck(const tlcg_model* m);
  * the per-lane pass refuses this model (as it must when *overflow),
  * -(1 + position) of the first code that disagrees, -1 on a bad model. */
 int64_t tlcg_host_lane_owner_selfcheck(const tlcg_model* m, int* overflow);
+/* The per-lane kernel's prefix form replayed on the host: how many of the
+ * components [first, first + n) (clipped to the model's initial states) run
+ * their FIFO BFS, in the kernel's order, through S's codes in dense order --
+ * the root has dense index 0 and every newly inserted code has dense index =
+ * the queue's length before it.  These are the components that form keeps;
+ * the others go on to the cascade.  Returns 0 when the per-lane pass refuses
+ * this model, -1 on a bad model.  Host only. */
+int64_t tlcg_host_lane_prefix_selfcheck(const tlcg_model* m, uint64_t first, uint64_t n);
 /* The first word of the owner entry of an arbitrary component code (0: a
  * field does not fit), -1 on a bad model.  Host only. */
 int64_t tlcg_host_lane_owner_word(const tlcg_model* m, uint32_t code);

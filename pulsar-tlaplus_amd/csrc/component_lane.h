@@ -69,7 +69,41 @@
 //     one copy after they join (a copy in each form spilled), and the first
 //     event of a batch goes to the result at the batch's end instead of
 //     riding in two registers across every batch.
-// LDS per 64-lane workgroup: the ring R x 256 B (the host picks R per layout,
+//   - round 10 (TLCG_LANE_PREFIX): the second word of an owner entry, the
+//     code's dense index, is its position in S's own FIFO BFS walked in this
+//     kernel's order (compactor successor, then BrokerCrash's, each appended
+//     when new).  A component that walks S in that order inserts the code
+//     with dense index `tail` at queue position `tail`, every time, so the
+//     64-bit set and the ring re-derive what one comparison against `tail`
+//     decides.  The lane keeps neither: FPSet.put of a successor t is its
+//     probe as before (the lane's own t, lane_slot, owner[p], low half against
+//     t + 1), then with d the entry's dense index: d < tail: in the set;
+//     d == tail: new, at position tail; any other d: this component does not
+//     walk S in S's order, and it goes to the cascade as one with a successor
+//     outside S does (`out`: the expansion's inserts masked, the levels
+//     counted so far kept).  The state to expand is byidx[head], a shared
+//     table of S's owner words by dense index filled from owner[] at start.
+//     This is exact for any component, by induction over the inserts on
+//       I(tail): the lane's set is {codes of S with dense index < tail}, and
+//                queue position i holds the code with dense index i, i < tail.
+//     The root is checked to be S's code of dense index 0, so I(1) holds (or
+//     the lane leaves before it expands anything).  Given I(tail) and a
+//     successor t: the slot hash is injective on S, so the low half of
+//     owner[slot(t)] is t + 1 exactly when t is in S, and then d is t's dense
+//     index.  t outside S is not in a set of codes of S: the lane leaves, as
+//     before this round.  d < tail: t is in the set by I(tail), nothing
+//     changes.  d == tail: t is not in the set by I(tail) (dense indices are a
+//     bijection), it is appended at position tail, and I(tail + 1) holds.
+//     d > tail: t is new, but appending it would break I, so the lane leaves
+//     with nothing of this expansion inserted.  The second successor of an
+//     expansion is judged against the prefix after the first's insert
+//     (tail + new1); when both are the same code the second finds d < tail +
+//     1.  A lane that stays therefore computed, at every insert, exactly
+//     what a private set and queue would have; nothing is assumed of the
+//     component, and no successor is read from a table: each lane still
+//     steps, hashes and probes its own state's successors.
+// LDS per 64-lane workgroup (TLCG_LANE_PREFIX: byidx 0.25 KB instead of the
+// ring, 3072 B; below, the figures without it): the ring R x 256 B (the host picks R per layout,
 // jit.cpp / host_model.cpp lane_ring_entries: 8 entries, 2 KB, on G9; a wider
 // frontier sends the component to the cascade), owner 2 KB, the step table
 // 0.5 KB, the level sums 0.25 KB: 4864 B as before round 8 (then the ring 1
@@ -132,6 +166,21 @@ constexpr int LANE_R = TLCG_LANE_R;  // FIFO ring entries per lane (a power of 2
 #ifndef TLCG_LANE_CRASH_SKIP
 #define TLCG_LANE_CRASH_SKIP 1
 #endif
+// round 10: the lane's FPSet and FIFO as a prefix of S's dense order, verified
+// at every insert (the header comment): membership is `dense index < tail`,
+// the state to expand is byidx[head]; no fp register, no ring.  0: round 9's
+// kernel (A/B).  It needs the two-word owner entry and the owner word.
+#ifndef TLCG_LANE_PREFIX
+#define TLCG_LANE_PREFIX 1
+#endif
+#if !TLCG_LANE_FP_REG || !TLCG_LANE_OWNER_RING
+#undef TLCG_LANE_PREFIX
+#define TLCG_LANE_PREFIX 0
+#endif
+// test only, TLCG_LANE_PREFIX_BREAK=p: the insert at queue position p counts
+// as one out of order, so every lane leaves for the cascade there, mid-wave,
+// with the levels it has counted (no cfg of the spec is known to take that
+// path by itself)
 
 // which form of the expansion component_lane_body's `expand` compiles
 template <bool B>
@@ -163,7 +212,14 @@ __device__ __forceinline__ void component_lane_body(const CompArgs& a, const Lay
 #else
   typedef uint16_t ring_t;                     // (codes)
 #endif
+#if TLCG_LANE_PREFIX
+  // S in dense order: byidx[d] = the owner word of the code with dense index d
+  // (0 past |S|), shared: a lane's queue position i holds byidx[i]
+  __shared__ uint32_t byidx[64];
+  (void)R;
+#else
   __shared__ ring_t ring[R][64];               // the lanes' FIFOs (unexpanded states)
+#endif
 #if TLCG_LANE_FP_REG
   __shared__ u64 owner[T];                     // slot s: its owner word (0: none) | dense index << 32, shared
 #else
@@ -192,6 +248,14 @@ __device__ __forceinline__ void component_lane_body(const CompArgs& a, const Lay
 #endif
   if (lane < LVS) lvl_sh[lane] = 0;
   uint32_t gen = 0, dist = 0, nexp = 0;  // (nexp: states expanded by the components that finish here)
+#if TLCG_LANE_PREFIX
+  byidx[lane] = 0u;
+  __syncthreads();
+  for (int i = lane; i < T; i += 64) {
+    const uint32_t w = a.lane_owner[2 * i], d = a.lane_owner[2 * i + 1];
+    if (w && d < 64u) byidx[d] = w;  // (the dense indices are a bijection onto 0..|S| - 1: one writer each)
+  }
+#endif
   __syncthreads();
   // a level's per-lane counts (x: distinct | generated << 16) into lvl_sh: one
   // LDS add per adding lane (round 8: at 20 level ends per 62 iterations the
@@ -220,7 +284,9 @@ __device__ __forceinline__ void component_lane_body(const CompArgs& a, const Lay
     const u64 entry = act ? (a.list ? a.list[ci] : a.comp0 + ci) : 0;
     const u64 idx0 = entry & ((1ull << 40) - 1);
     const int counted = (int)(entry >> 40);
-#if TLCG_LANE_FP_REG
+#if TLCG_LANE_PREFIX
+    // (the lane's FPSet is the codes of S with dense index < tail)
+#elif TLCG_LANE_FP_REG
     u64 fp = 0;  // the lane's FPSet: bit d = the code of S with dense index d
 #else
 #pragma unroll
@@ -254,18 +320,27 @@ __device__ __forceinline__ void component_lane_body(const CompArgs& a, const Lay
     const ckey c0 = code_encode(L, k0);
     const unsigned p0 = lane_slot(c0, mult);
     const uint32_t ow0 = (uint32_t)owner[p0];
-    if (act && (code_decode(L, ccon, c0) != k0 || (ow0 & 0xFFFFu) != c0 + 1u)) {
+#if TLCG_LANE_PREFIX
+    // (the prefix starts at the root: S's code of dense index 0)
+    const bool root_ok = (ow0 & 0xFFFFu) == c0 + 1u && (uint32_t)(owner[p0] >> 32) == 0u;
+#else
+    const bool root_ok = (ow0 & 0xFFFFu) == c0 + 1u;
+#endif
+    if (act && (code_decode(L, ccon, c0) != k0 || !root_ok)) {
       // no code, or not the code graph the slots were built for: the cascade
       ovf = true;
       alive = false;
     }
     if (alive) {
-#if TLCG_LANE_FP_REG
+#if TLCG_LANE_PREFIX
+      // (position 0 is byidx[0], the set is [0, tail))
+#elif TLCG_LANE_FP_REG
       fp = 1ull << (uint32_t)(owner[p0] >> 32);
 #else
       bits[p0 >> 5][lane] = 1u << (p0 & 31);
 #endif
-#if TLCG_LANE_OWNER_RING
+#if TLCG_LANE_PREFIX
+#elif TLCG_LANE_OWNER_RING
       ring[0][lane] = ow0;
 #else
       ring[0][lane] = (uint16_t)c0;
@@ -292,7 +367,11 @@ __device__ __forceinline__ void component_lane_body(const CompArgs& a, const Lay
       // (a finished lane goes on with whatever its ring holds: the index is
       // kept inside the table, every slot is below T)
       const ckey s = (cur & 0xFFFFu) - 1u;
+#if TLCG_LANE_PREFIX
+      uint32_t nxt = 0;
+#else
       uint32_t nxt = 0, first_new = 0;
+#endif
 #else
       const ckey s = cur;
       ckey nxt = 0, first_new = 0;
@@ -305,7 +384,15 @@ __device__ __forceinline__ void component_lane_body(const CompArgs& a, const Lay
       ckey t = 0;
       int action = 0;
 #if TLCG_LANE_OWNER_RING
+#if TLCG_LANE_PREFIX
+      // the next state to expand: position head + 1 holds S's code of that
+      // dense index whatever this expansion inserts, so the read goes out
+      // with the step entry's (the lanes of a wave read one address: a
+      // broadcast; a finished lane's index stays inside the table)
+      nxt = byidx[(head + 1) & 63];
+#else
       nxt = ring[(head + 1) & (R - 1)][lane];
+#endif
       const uint32_t six = (cur >> LANE_OWNER_STEP_SH) & (uint32_t)(STEP_TAB - 1);
       uint32_t term = 0;
       const int r = compactor_step_ent(L, ccon, steps[six], six & 7u, s, &t, &action, &term);  // compaction.tla:221-226
@@ -347,7 +434,31 @@ __device__ __forceinline__ void component_lane_body(const CompArgs& a, const Lay
         // a successor outside the code set: this component is not S's, the cascade
         out = (e1 && !in1) || (e2 && !in2);
         bool new2 = false;
-#if TLCG_LANE_FP_REG
+#if TLCG_LANE_PREFIX
+        // FPSet.put against the prefix [0, tail): a code of S with dense index
+        // d is in the set iff d < tail; one not in it must be the next of S's
+        // order (d == tail, for the second successor after the first's
+        // insert), or this component does not walk S in S's order: the
+        // cascade, as for a successor outside S
+        const uint32_t d1 = (uint32_t)(oe1 >> 32), ut = (uint32_t)tail;
+        const bool n1 = e1 && in1 && d1 >= ut;
+        bool bad = n1 && d1 != ut;
+#ifdef TLCG_LANE_PREFIX_BREAK
+        bad = bad || (n1 && tail == (TLCG_LANE_PREFIX_BREAK));
+#endif
+        bool n2 = false;
+        if constexpr (W2) {
+          const uint32_t d2 = (uint32_t)(oe2 >> 32), ut2 = ut + (n1 ? 1u : 0u);
+          n2 = e2 && in2 && d2 >= ut2;
+          bad = bad || (n2 && d2 != ut2);
+#ifdef TLCG_LANE_PREFIX_BREAK
+          bad = bad || (n2 && (int)ut2 == (TLCG_LANE_PREFIX_BREAK));
+#endif
+        }
+        out = out || bad;
+        const bool new1 = n1 && !out;
+        new2 = n2 && !out;
+#elif TLCG_LANE_FP_REG
         // (a dense index is below 62: build_lane_phash)
         const u64 b1 = 1ull << (uint32_t)(oe1 >> 32);
         const bool new1 = e1 && in1 && !(fp & b1) && !out;
@@ -370,7 +481,9 @@ __device__ __forceinline__ void component_lane_body(const CompArgs& a, const Lay
 #endif
         // the queue (the ring: a successor not inserted is overwritten or never
         // read) and each new state's record at its position
-#if TLCG_LANE_OWNER_RING
+#if TLCG_LANE_PREFIX
+        // (no queue to write: position tail holds byidx[tail], just verified)
+#elif TLCG_LANE_OWNER_RING
         ring[tail & (R - 1)][lane] = o1;
         if constexpr (W2) ring[(tail + (new1 ? 1 : 0)) & (R - 1)][lane] = o2;
 #else
@@ -385,7 +498,8 @@ __device__ __forceinline__ void component_lane_body(const CompArgs& a, const Lay
                                                 new2 ? (int)((unsigned)(tail + (new1 ? 1 : 0)) * 256u + loff) : OOB,
                                                 0, 0);
 #endif
-#if TLCG_LANE_OWNER_RING
+#if TLCG_LANE_PREFIX
+#elif TLCG_LANE_OWNER_RING
         first_new = W2 ? (new1 ? o1 : o2) : o1;
 #else
         first_new = W2 ? (new1 ? t : t2) : t;
@@ -454,7 +568,13 @@ __device__ __forceinline__ void component_lane_body(const CompArgs& a, const Lay
         }
       }
       if (alive) ++head;
+#if TLCG_LANE_PREFIX
+      // (a live lane's head went up by one; a finished lane expands nothing,
+      // whatever it holds)
+      cur = nxt;
+#else
       cur = head < tail0 ? nxt : first_new;  // position head was filled by this expansion
+#endif
       bool brk = alive && head >= tail;      // the component ran out
       // level `level` = [lvl_start, lvl_end) complete and expanded
       const bool ended = alive && head == lvl_end;
@@ -475,7 +595,14 @@ __device__ __forceinline__ void component_lane_body(const CompArgs& a, const Lay
       // room for both successors of the next expansion, in the records and
       // in the ring (checked once per expansion; a component of K - 1 or K
       // states goes on to the cascade too)
+#if TLCG_LANE_PREFIX
+      // (no ring to fill; every insert had dense index tail, and a dense index
+      // is below 62 (build_lane_phash, and byidx holds 64), so tail <= 62 =
+      // K - 2 at K = 64: the test is left to a smaller K)
+      const bool full = K < 64 && alive && !brk && tail > K - 2;
+#else
       const bool full = alive && !brk && (tail > K - 2 || tail - head > R - 2);
+#endif
       ovf = ovf || full || out;
       alive = alive && !(brk || full || out);
     }

@@ -1096,6 +1096,52 @@ int64_t tlcg_host_lane_owner_selfcheck(const tlcg_model* m, int* overflow) {
   return (int64_t)q.size();
 }
 
+// The per-lane kernel's prefix form (component_lane.h, round 10) replayed on
+// the host: the components of [first, first + n) whose FIFO BFS in the
+// kernel's order (compactor successor, then BrokerCrash's, each appended when
+// new) starts at S's code of dense index 0 and finds, at every insert, the
+// owner entry of the inserted code with dense index = the queue's length --
+// the test the kernel makes, through the same table and slot hash.  These are
+// the components the prefix form keeps; the others go to the cascade.
+// Components past the model's last are not counted.  Returns 0 when
+// build_lane_phash refuses the model, -1 on a bad model.
+int64_t tlcg_host_lane_prefix_selfcheck(const tlcg_model* m, uint64_t first, uint64_t n) {
+  HostModel hm;
+  std::string e;
+  if (!m || !build_model(*m, &hm, &e)) return -1;
+  const Layout& L = hm.L;
+  std::vector<uint32_t> owner(2 * LANE_T);
+  uint32_t mult = 0;
+  if (!build_lane_phash(hm, &mult, owner.data(), nullptr)) return 0;
+  // the entry of code c: its dense index, or -1 when c is not in S
+  auto dense = [&](ckey c) -> int64_t {
+    const unsigned sl = lane_slot(c, mult);
+    return (owner[2 * sl] & 0xFFFFu) == c + 1u ? (int64_t)owner[2 * sl + 1] : -1;
+  };
+  int64_t kept = 0;
+  for (u64 idx = first; idx < first + n && idx < hm.n_init; ++idx) {
+    const u128 s0 = init_state<u128>(L, idx);
+    const CodeConsts kc = code_consts(L, comp_msgs_init(L, (u64)s0));
+    std::vector<ckey> q{code_encode_w<u128>(L, s0)};
+    // (the set is kept on its own here, so "new" is not the kernel's d >= tail)
+    std::unordered_set<uint32_t> seen{q[0]};
+    bool ok = dense(q[0]) == 0;
+    auto put = [&](ckey t) {
+      if (!seen.insert(t).second) return;
+      ok = ok && dense(t) == (int64_t)q.size();
+      q.push_back(t);
+    };
+    for (size_t head = 0; ok && head < q.size(); ++head) {
+      ckey t = 0, t2 = 0;
+      int act = 0;
+      if (compactor_step_cb(L, kc, q[head], &t, &act) == 1) put(t);
+      if (ok && crash_step_c(L, q[head], &t2)) put(t2);
+    }
+    kept += ok ? 1 : 0;
+  }
+  return kept;
+}
+
 // word 0 of the owner entry of an arbitrary code (component_code.h
 // lane_owner_word; 0: a field does not fit), -1 on a bad model
 int64_t tlcg_host_lane_owner_word(const tlcg_model* m, uint32_t code) {

@@ -93,7 +93,10 @@ bool build_slot_owner(const HostModel& hm, int T, uint32_t mult, uint32_t dmult,
 // and the owner table, LANE_T entries of two words: owner[2 s] = (the code in
 // slot s + 1) | its invariant features << 16 | its step-table index << 25
 // (component_code.h lane_owner_word; 0: no code), owner[2 s + 1] = the code's
-// dense index in the set (its BFS position).  The first multiplier of a fixed
+// dense index in the set (its position in component 0's FIFO BFS walked in
+// the kernel's order: the compactor's successor, then BrokerCrash's; the
+// kernel's prefix form, TLCG_LANE_PREFIX, keeps a component only while its own
+// inserts follow that order, tlcg_host_lane_prefix_selfcheck).  The first multiplier of a fixed
 // sequence that works; false when the component has 63 or more states (the
 // pass's capacity), a field of some code's entry does not fit, no multiplier
 // was found, or the features and a component's mask do not give
@@ -104,6 +107,7 @@ bool build_lane_phash(const HostModel& hm, uint32_t* mult, uint32_t* owner, std:
 // queue (the kernel sends a component on to the cascade once tail - head >
 // R - 2 after an expansion), 16 when that does not fit or the model has no
 // per-lane pass.  Depends on the layout alone (component 0's closure).
+// (The kernel's prefix form has no ring: LANE_R matters with TLCG_LANE_PREFIX=0.)
 int lane_ring_entries(const Layout& L);
 
 // every invariant of the cfg, the user's included: -1, else (index << 1) | is_error

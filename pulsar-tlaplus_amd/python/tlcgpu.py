@@ -127,6 +127,7 @@ def load_library(path: str = LIB_PATH):
         "tlcg_host_lane_inv_selfcheck": (C.c_int64, [M]),
         "tlcg_host_lane_owner_selfcheck": (C.c_int64, [M, C.POINTER(C.c_int)]),
         "tlcg_host_lane_owner_word": (C.c_int64, [M, C.c_uint32]),
+        "tlcg_host_lane_prefix_selfcheck": (C.c_int64, [M, U64, U64]),
         "tlcg_host_tree_slot_probes": (C.c_int, [M, U64, C.POINTER(C.c_int64)]),
         "tlcg_host_termination_counterexample": (C.c_int64, [M]),
         "tlcg_owner": (C.c_int, [P, U64]),
@@ -373,6 +374,14 @@ def host_lane_owner_selfcheck(model: Model):
     ovf = C.c_int(0)
     n = load_library().tlcg_host_lane_owner_selfcheck(C.byref(m), C.byref(ovf))
     return n, bool(ovf.value)
+
+
+def host_lane_prefix_selfcheck(model: Model, first: int, n: int) -> int:
+    """Components of [first, first + n) that the per-lane kernel's prefix form
+    keeps: their FIFO BFS in the kernel's order inserts S's codes in dense
+    order at every insert (0: the per-lane pass refuses the model)."""
+    m = model.to_c()
+    return load_library().tlcg_host_lane_prefix_selfcheck(C.byref(m), C.c_uint64(first), C.c_uint64(n))
 
 
 def host_lane_owner_word(model: Model, code: int) -> int:
