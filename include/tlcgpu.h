@@ -74,7 +74,10 @@ enum {
   TLCG_VIOLATION = 2,        /* "Invariant X is violated." */
   TLCG_DEADLOCK = 3,         /* "Deadlock reached." */
   TLCG_ACTION_ERROR = 4,     /* evaluation error while computing a successor */
-  TLCG_INVARIANT_ERROR = 5   /* evaluation error while evaluating an invariant */
+  TLCG_INVARIANT_ERROR = 5,  /* evaluation error while evaluating an invariant */
+  TLCG_CONSTRAINT_ERROR = 6  /* evaluation error while evaluating a state constraint (cfg CONSTRAINT):
+                                tlcg_stats.invariant is then the index of the constraint among the
+                                @@CONSTRAINT lines, the trace ends in the state it failed on */
 };
 
 /* The constants of compaction.tla:10-18 as bound by a TLC cfg
@@ -106,7 +109,27 @@ typedef struct tlcg_model {
    * global engine in a check kernel over each new level (TLCG_JIT=0 leaves
    * such models to the global engine).  The text is copied by tlcg_create.  (ModelChecker's
    * invariant list, compaction.cfg:25-31, with invariants the user defined
-   * in the .tla, compaction.tla:236-294 being the spec's own.) */
+   * in the .tla, compaction.tla:236-294 being the spec's own.)
+   *
+   * State constraints (a cfg's CONSTRAINT / CONSTRAINTS section) travel in
+   * the same text: a line "@@CONSTRAINT <name>" (anywhere outside a
+   * definition's body; the Python face and tlc-hip put them last) names a
+   * definition given by an @@DEF block, without parameters, as a constraint.
+   * Several are a conjunction, evaluated in their order; a definition may be
+   * an invariant and a constraint.  The same subset and the same refusals as
+   * user invariants.  Semantics [TLC-ext: restated from TLC's worker, not
+   * confirmable without TLC]: every successor (and every initial state) counts
+   * as generated and spares its parent the deadlock; a successor that is new
+   * or violates a constraint has every invariant checked on it, so a
+   * violation on a state about to be discarded is reported, its trace ending
+   * there; only states that satisfy every constraint are counted as distinct,
+   * stored and expanded; depth counts the non-empty levels of kept states.  An
+   * evaluation error of a constraint stops the run (TLCG_CONSTRAINT_ERROR).
+   * When the run stops on an error at level E that level is still filtered;
+   * tlcg_stats.tlc_exact is 0 and tlcg_tlc_stop_stats / tlcg_outdegree refuse.
+   * Taken by the global engine on one rank (AUTO picks it; an explicit
+   * on-chip engine, world > 1, spill and fpset_spill are refused at
+   * tlcg_create, the property passes by their own calls). */
   const char* user_defs;
 } tlcg_model;
 
@@ -265,6 +288,15 @@ int tlcg_expansions(tlcg_ctx* c, uint64_t* out);
  * stopped at different levels needs, tlcg_run_node / dist.py).  Refused after
  * tlcg_recover (the checkpoint holds only the total). */
 int tlcg_level_generated(tlcg_ctx* c, uint64_t* out, int32_t cap, int32_t* n);
+/* The constraint pass of the run so far (global engine, a model with a
+ * CONSTRAINT): *discarded = states generated as new and dropped by it (a state
+ * found again after an FPSet rebuild counts again), *pass_ms = device time of
+ * the pass (both kernels and the scan between them; a part of
+ * tlcg_stats.kernel_ms), level_ms[k] = its share on level k, *n = levels it
+ * ran on.  Any pointer may be NULL.  Zeros without a constraint; counted from
+ * tlcg_init or tlcg_recover on. */
+int tlcg_constraint_stats(tlcg_ctx* c, uint64_t* discarded, double* pass_ms, float* level_ms, int32_t cap,
+                          int32_t* n);
 /* Successor ordinal bits (to split a parent_ref). */
 int tlcg_ordinal_bits(const tlcg_model* m);
 int tlcg_action_of_ordinal(const tlcg_model* m, int32_t ordinal);
@@ -288,6 +320,14 @@ int tlcg_host_check_invariants_words(const tlcg_model* m, const uint64_t* state)
 /* The same for n states (tlcg_state_words words each) into out[i]: one model
  * build (and user-invariant compile) for the batch.  0, or -2 on a bad model. */
 int tlcg_host_check_invariants_batch(const tlcg_model* m, const uint64_t* states, uint64_t n, int32_t* out);
+/* The conjunction of the model's state constraints (@@CONSTRAINT lines of
+ * user_defs) on n states (tlcg_state_words words each), by the host
+ * interpreter: out[i] = 0 TRUE (the state is in the model), 1 FALSE, 2 an
+ * evaluation error (of the first constraint, in their order, that is not
+ * TRUE).  All 0 for a model without a constraint.  0; -1 a null argument; -2
+ * a bad model (message in err). */
+int tlcg_host_constraint_eval(const tlcg_model* m, const uint64_t* states, uint64_t n, uint8_t* out, char* err,
+                              int32_t errlen);
 /* Self-check of the component engine's specialized evaluators against the
  * generic ones on the components of initial states [first, first + n), host
  * only.  Returns the states compared (0: the component engine does not take

@@ -124,13 +124,14 @@ bool build_model(const tlcg_model& m, HostModel* out, std::string* err) {
     if (k == names.size()) names.push_back(nm);
     L.inv[q] = INV_USER + (int)k;
   }
-  if (!names.empty()) {
+  hm.constraints = user_constraint_names(m.user_defs);
+  if (!names.empty() || !hm.constraints.empty()) {
     auto prog = std::make_shared<UserProg>();
     std::string e;
-    if (!compile_user_invariants(m, hm, names, prog.get(), &e)) return fail(e);
+    if (!compile_user_invariants(m, hm, names, prog.get(), &e, hm.constraints)) return fail(e);
     hm.user = prog;
     hm.user_defs = m.user_defs;
-    L.defer_inv = 1;
+    L.defer_inv = names.empty() ? 0 : 1;
   }
   *out = hm;
   return true;
@@ -722,6 +723,28 @@ int tlcg_host_check_invariants_batch(const tlcg_model* m, const uint64_t* states
   if (!m || !states || !out || !build_model(*m, &hm, &e)) return -2;
   const int w = state_words(hm.L);
   for (uint64_t i = 0; i < n; ++i) out[i] = host_check_all<u128>(hm, join_words(states + i * (uint64_t)w, w));
+  return 0;
+}
+
+int tlcg_host_constraint_eval(const tlcg_model* m, const uint64_t* states, uint64_t n, uint8_t* out, char* err,
+                              int32_t errlen) {
+  auto fail = [&](int rc, const std::string& e) {
+    if (err && errlen > 0) std::snprintf(err, (size_t)errlen, "%s", e.c_str());
+    return rc;
+  };
+  HostModel hm;
+  std::string e;
+  if (!m || !states || !out) return fail(-1, "null argument");
+  if (!build_model(*m, &hm, &e)) return fail(-2, e);
+  const int w = state_words(hm.L);
+  for (uint64_t i = 0; i < n; ++i) {
+    int which = 0;
+    out[i] = hm.constraints.empty()
+                 ? (uint8_t)EV_TRUE
+                 : (uint8_t)eval_constraints_v(*hm.user, UVWord<u128>{hm.L, join_words(states + i * (uint64_t)w, w)},
+                                               &which);
+  }
+  if (err && errlen > 0) err[0] = 0;
   return 0;
 }
 

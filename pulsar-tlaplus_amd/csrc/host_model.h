@@ -18,15 +18,19 @@ struct HostModel {
   std::vector<int64_t> valueset;  // ValueSet = ValueSpace \cup {0}, sorted
   u64 n_init;                     // number of initial states
   int max_new_per_state;          // upper bound on distinct successors of one state
-  std::shared_ptr<UserProg> user;  // the user invariants' program (user_inv.h), or null
+  std::shared_ptr<UserProg> user;  // the user invariants' (and constraints') program (user_inv.h), or null
+  std::vector<std::string> constraints;  // the state constraints' names (cfg CONSTRAINT), program entries n_user ..
   std::string user_defs;          // their text (tlcg_model.user_defs)
 };
 
 // Compiles the user invariants `names` (definitions of m.user_defs) into *P
 // (user_inv.cpp); false with a message otherwise.
 bool compile_user_invariants(const tlcg_model& m, const HostModel& hm, const std::vector<std::string>& names,
-                             UserProg* P, std::string* err);
+                             UserProg* P, std::string* err,
+                             const std::vector<std::string>& constraints = std::vector<std::string>());
 std::vector<std::string> user_def_names(const char* text);
+// the cfg's CONSTRAINT names: the "@@CONSTRAINT <name>" lines of the text
+std::vector<std::string> user_constraint_names(const char* text);
 // The temporal front end (user_inv.cpp): classifies definition `name` of
 // m.user_defs as <>Q, []<>Q or P ~> Q (*form = TLCG_PROP_*) and compiles its
 // operands into *P, entry 0 = P (the constant TRUE for the forms without one),

@@ -88,6 +88,9 @@ std::string program_source(const Layout& L, const std::string& user, int part = 
   if (check_only) {
     s += "extern \"C\" __global__ __launch_bounds__(256) void tlcg_user_check(tlcg::UserCheckArgs a) "
          "{ tlcg::user_check_body<" + w + ">(a, kL); }\n";
+    // kernel 1 of the constraint pass (cfg CONSTRAINT), beside it
+    s += "extern \"C\" __global__ __launch_bounds__(256) void tlcg_constraint_eval(tlcg::ConstraintArgs a) "
+         "{ tlcg::constraint_eval_body<" + w + ">(a, kL); }\n";
     return s;
   }
   if (part == JIT_EVAL) {
@@ -283,6 +286,10 @@ bool jit_build_user_check(const Layout& L, int device, const std::string& user, 
     *err = "hipModuleGetFunction tlcg_user_check";
     return false;
   }
+  if (hipModuleGetFunction(&out->fn_constraint, out->module, "tlcg_constraint_eval") != hipSuccess) {
+    *err = "hipModuleGetFunction tlcg_constraint_eval";
+    return false;
+  }
   return true;
 }
 
@@ -298,6 +305,16 @@ bool jit_launch_user_check(const JitUserCheck& k, const UserCheckArgs& a, hipStr
   UserCheckArgs copy = a;
   void* args[] = {&copy};
   return hipModuleLaunchKernel(k.fn, (unsigned)blocks, 1, 1, 256, 1, 1, 0, stream, args, nullptr) == hipSuccess;
+}
+
+bool jit_launch_constraint_eval(const JitUserCheck& k, const ConstraintArgs& a, hipStream_t stream) {
+  if (!a.u.n) return true;
+  const uint64_t blocks = (a.u.n + 255) / 256;
+  if (blocks > 0x7fffffffull || !k.fn_constraint) return false;
+  ConstraintArgs copy = a;
+  void* args[] = {&copy};
+  return hipModuleLaunchKernel(k.fn_constraint, (unsigned)blocks, 1, 1, 256, 1, 1, 0, stream, args, nullptr) ==
+         hipSuccess;
 }
 
 bool jit_build_user_eval(const Layout& L, int device, const std::string& user, JitUserCheck* out, std::string* err) {

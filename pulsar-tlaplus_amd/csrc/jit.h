@@ -64,11 +64,14 @@ bool jit_launch_component(const JitKernels& k, const CompArgs& a, int K, bool co
 struct JitUserCheck {
   hipModule_t module = nullptr;
   hipFunction_t fn = nullptr;
+  hipFunction_t fn_constraint = nullptr;  // tlcg_constraint_eval (kernels.h constraint_eval_body), the same module
   double compile_s = 0;
 };
 bool jit_build_user_check(const Layout& L, int device, const std::string& user, JitUserCheck* out, std::string* err);
 void jit_release_user_check(JitUserCheck* k);
 bool jit_launch_user_check(const JitUserCheck& k, const UserCheckArgs& a, hipStream_t stream);
+// kernel 1 of the constraint pass, one block of 256 per block_cnt entry
+bool jit_launch_constraint_eval(const JitUserCheck& k, const ConstraintArgs& a, hipStream_t stream);
 // the test hook's kernel (JIT_EVAL), in a module of its own: the modules a check loads hold no kernel of it
 bool jit_build_user_eval(const Layout& L, int device, const std::string& user, JitUserCheck* out, std::string* err);
 bool jit_launch_user_eval(const JitUserCheck& k, const UserEvalArgs& a, hipStream_t stream);

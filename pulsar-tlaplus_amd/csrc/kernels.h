@@ -217,6 +217,50 @@ __device__ __forceinline__ void user_check_body(const UserCheckArgs& a, const La
 }
 #endif
 
+// ---- the global engine's constraint pass over a new level [g0, g0 + n) (cfg
+// CONSTRAINT): kernel 1 evaluates the conjunction of the constraints on each
+// state, one lane per state, writes the lane's keep flag and adds each
+// wave's kept count (ballot + popcount) to its block's count; a scan of the
+// block counts and k_constraint_scatter (tlcgpu.hip) then pack the kept states
+// in their order.  An evaluation error raises an event keyed like a user
+// invariant's (user_check_dkey), index = the failing constraint.  The
+// precompiled k_constraint_eval interprets the program; the hipRTC build
+// (jit.cpp tlcg_constraint_eval) runs it as device code.
+struct ConstraintArgs {
+  UserCheckArgs u;                 // the level (u.ev: the constraint-error event, min)
+  uint8_t* keep;                   // [n] 1: the state stays in the model
+  unsigned long long* block_cnt;   // [blocks] kept states of each block
+};
+
+// the tail both forms share; every thread of the block reaches it
+template <typename W>
+__device__ __forceinline__ void constraint_commit(const Layout& L, const ConstraintArgs& a, u64 i, bool valid, int r,
+                                                  int which, W s) {
+  __shared__ unsigned s_kept;
+  if (threadIdx.x == 0) s_kept = 0;
+  __syncthreads();
+  if (valid && r == EV_ERROR)
+    atomicMin(a.u.ev, (unsigned long long)make_event(user_check_dkey(L, a.u, i, s), EVK_INV_ERROR, which));
+  const bool keep = valid && r == EV_TRUE;
+  if (valid) a.keep[i] = keep ? 1 : 0;
+  const u64 m = __ballot(keep);
+  if (m && __lane_id() == __ffsll((long long)m) - 1) atomicAdd(&s_kept, (unsigned)__popcll(m));
+  __syncthreads();
+  if (threadIdx.x == 0) a.block_cnt[blockIdx.x] = s_kept;
+}
+
+#ifdef TLCG_USER_INV
+template <typename W>
+__device__ __forceinline__ void constraint_eval_body(const ConstraintArgs& a, const Layout& L) {
+  const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool valid = i < a.u.n;
+  const W s = valid ? ((const W*)a.u.states)[i] : (W)0;
+  int which = 0;
+  const int r = valid ? tlcg_constraints_eval(UVWord<W>{L, s}, &which) : (int)EV_FALSE;
+  constraint_commit<W>(L, a, i, valid, r, which, s);
+}
+#endif
+
 // ---- test hook (tlcg_user_eval_selftest): every user invariant on each of n
 // given states, one thread per state, out[i * n_user + k] = EV_* of invariant
 // k on state i.  path 1: the generated code over the word (what

@@ -1311,6 +1311,8 @@ extern "C" int tlcg_check_termination(const tlcg_model* m, const tlcg_opts* o, i
   HostModel hm;
   std::string e;
   if (!build_model(*m, &hm, &e)) return fail(-3, e);
+  if (!hm.constraints.empty())
+    return fail(-2, "the model has a CONSTRAINT: PROPERTY Termination is not checked under a state constraint");
   if (hipSetDevice(o ? o->device : 0) != hipSuccess) return fail(-4, "hipSetDevice failed");
   const auto t0 = std::chrono::steady_clock::now();
   LvTrace tr;
@@ -1394,6 +1396,8 @@ extern "C" int tlcg_check_property(const tlcg_model* m, const tlcg_opts* o, int3
   HostModel hm;
   std::string e;
   if (!build_model(*m, &hm, &e)) return fail(-3, e);
+  if (!hm.constraints.empty())
+    return fail(-2, "the model has a CONSTRAINT: a temporal PROPERTY is not checked under a state constraint");
   const std::unique_ptr<UserProg> prog(new UserProg);
   int form = 0;
   if (compile_property(*m, hm, name, &form, prog.get(), &e) != 0) return fail(-2, e);
@@ -1668,6 +1672,8 @@ extern "C" int tlcg_check_action_property(const tlcg_model* m, const tlcg_opts* 
   HostModel hm;
   std::string e;
   if (!build_model(*m, &hm, &e)) return fail(-3, e);
+  if (!hm.constraints.empty())
+    return fail(-2, "the model has a CONSTRAINT: an action PROPERTY is not checked under a state constraint");
   const std::unique_ptr<UserProg> prog(new UserProg);
   if (compile_action_property(*m, hm, name, nullptr, prog.get(), &e) != 0) return fail(-2, e);
   if (hipSetDevice(o ? o->device : 0) != hipSuccess) return fail(-4, "hipSetDevice failed");

@@ -78,6 +78,11 @@ constexpr int INV_USER = 16;
 // UVCode in component_code.h).  Returns EV_TRUE / EV_FALSE / EV_ERROR.
 template <class V>
 TLCG_HD int tlcg_user_eval(int k, const V& v);
+// The cfg's state constraints, a conjunction evaluated left to right: EV_TRUE
+// (the state is in the model), EV_FALSE, or EV_ERROR with *which = the
+// constraint that failed to evaluate.
+template <class V>
+TLCG_HD int tlcg_constraints_eval(const V& v, int* which);
 #endif
 
 // TLC's integers are 32-bit: a user invariant's +, -, * or unary - whose

@@ -83,6 +83,44 @@ __global__ __launch_bounds__(BLOCK) void k_user_eval(Layout L, const UserProg* _
   for (int k = 0; k < nu; ++k) out[i * (u64)nu + k] = (uint8_t)eval_user(L, *P, k, s);
 }
 
+// ---- state constraints (cfg CONSTRAINT): the pass over a new level
+// (kernels.h ConstraintArgs).  Kernel 1 with the interpreter, for TLCG_JIT=0 or
+// a failed hipRTC build (jit.cpp tlcg_constraint_eval is the generated form).
+template <typename W>
+__global__ __launch_bounds__(BLOCK) void k_constraint_eval(Layout L, const UserProg* __restrict__ P, ConstraintArgs a) {
+  const u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x;
+  const bool valid = i < a.u.n;
+  const W s = valid ? ((const W*)a.u.states)[i] : (W)0;
+  int which = 0;
+  const int r = valid ? eval_constraints_v(*P, UVWord<W>{L, s}, &which) : (int)EV_FALSE;
+  constraint_commit<W>(L, a, i, valid, r, which, s);
+}
+
+// Kernel 2: the kept states and their parent references to their packed
+// positions in scratch (never in place: a block's writes would land on states
+// another block has not read), in their order -- block_off is the exclusive
+// scan of kernel 1's block counts, the waves before this one in the block and
+// the lanes before this one in the wave (ballot, lanemask_lt) give the rest.
+template <typename W>
+__global__ __launch_bounds__(BLOCK) void k_constraint_scatter(const W* __restrict__ states,
+                                                              const u64* __restrict__ parents,
+                                                              const uint8_t* __restrict__ keep,
+                                                              const unsigned long long* __restrict__ block_off, u64 n,
+                                                              W* __restrict__ st_out, u64* __restrict__ par_out) {
+  __shared__ unsigned s_wave[BLOCK / 64];
+  const u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x;
+  const bool k = i < n && keep[i] != 0;
+  const u64 m = __ballot(k);
+  const int wv = threadIdx.x >> 6;
+  if (__lane_id() == 0) s_wave[wv] = (unsigned)__popcll(m);
+  __syncthreads();
+  if (!k) return;
+  u64 pos = block_off[blockIdx.x] + (u64)__popcll(m & lanemask_lt());
+  for (int j = 0; j < wv; ++j) pos += s_wave[j];
+  st_out[pos] = states[i];
+  par_out[pos] = parents[i];
+}
+
 // ---- error reporting on the device (tlcg_tlc_stop_stats, producer_error) ----
 constexpr int kScratch = 256;
 
@@ -1076,6 +1114,20 @@ struct tlcg_ctx {
   u64 tree_r0 = 0;                        //   of the components of initial states tree_r0, tree_r0 + 1, ..
   UserProg* d_prog = nullptr;            // the user invariants' program on the device (user_inv.h)
   unsigned long long* d_uev = nullptr;   // k_user_check's event (min)
+  // the constraint pass (cfg CONSTRAINT; constraint_level): its scratch, grown
+  // on demand and never allocated for a model without a constraint
+  unsigned long long* d_cev = nullptr;   // the constraint-error event (min)
+  uint8_t* d_ckeep = nullptr;            // [con_cap] keep flags
+  unsigned long long* d_ccnt = nullptr;  // [2][con_blocks + 1] block counts, their exclusive scan
+  void* d_ctmp = nullptr;                // the scan's scratch
+  size_t ctmp_bytes = 0;
+  u64* d_cst = nullptr;                  // [con_cap] the packed states / parent references, fast order
+  u64* d_cpar = nullptr;                 //   (TLC order packs into its sort scratch, d_st2 / d_dk2)
+  u64 con_cap = 0;
+  hipEvent_t ce0 = nullptr, ce1 = nullptr;
+  u64 con_discarded = 0;                 // states the pass discarded in this run
+  u64 con_in_fpset = 0;                  // ... that the FPSet still holds (it is sized for them too)
+  std::vector<float> con_level_ms;       // device time of the pass per level
   int words = 1;  // u64 words per state: 1, or 2 for wide layouts (> 63 bits)
   int device = 0;
   hipStream_t stream = nullptr;
@@ -1541,6 +1593,7 @@ bool rebuild_fpset(tlcg_ctx* c, int log2, u64 n) {
     c->log2 = log2;
   }
   HIPCHK(hipMemsetAsync(c->d_slots, 0, (8ull * c->words) << log2, c->stream));
+  c->con_in_fpset = 0;  // (the states a constraint discarded are not stored: later levels find them again)
   if (c->d_dkey_slot) HIPCHK(hipMemsetAsync(c->d_dkey_slot, 0xFF, 8ull << log2, c->stream));
   if (n > c->t0_base) {
     HIPCHK(hipMemsetAsync(c->d_aux, 0, sizeof(LevelCtr), c->stream));
@@ -1972,7 +2025,8 @@ void fill_stats(tlcg_ctx* c, tlcg_stats* st) {
   st->levels_redone = c->levels_redone;
   // the trace and tlcg_tlc_stop_stats are TLC -workers 1's: a TLC-order run,
   // or an on-chip engine's error on a closed partition (one rank)
-  st->tlc_exact = c->status >= TLCG_VIOLATION && c->opts.world == 1 &&
+  // (not under a constraint: TLC's own stop counters there are out of scope)
+  st->tlc_exact = c->status >= TLCG_VIOLATION && c->opts.world == 1 && c->hm.constraints.empty() &&
                   ((c->engine == TLCG_ENGINE_GLOBAL && c->opts.tlc_order) || c->stop_cached ||
                    (c->engine != TLCG_ENGINE_GLOBAL && !c->hm.L.producer && c->ev_comp != ~0ull));
 }
@@ -2373,8 +2427,10 @@ bool jit_off() {
 bool component_applicable(const tlcg_ctx* c) {
   const Layout& L = c->hm.L;
   const int mb = L.msg_sh + L.N * L.mw;
+  // (a constraint changes the reachable set: the closed components' code sets,
+  // perfect hashes and BFS positions do not hold under it -- the global engine)
   return !L.producer && !c->opts.tlc_order && c->closed && L.bits <= 63 && L.bits - mb <= 32 && L.N <= 8 &&
-         c->hm.n_init < (1ull << 36) && !(c->hm.user && jit_off());
+         c->hm.n_init < (1ull << 36) && !(c->hm.user && jit_off()) && c->hm.constraints.empty();
 }
 
 // Fold the COMP_STRIPES copies of a pass's counters into out[0, kCompCounters)
@@ -2628,7 +2684,8 @@ bool tree_applicable(const tlcg_ctx* c) {
   const char* tv = std::getenv("TLCG_TREE");
   return L.producer && !(tv && std::atoi(tv) == 0) && !c->no_tree && !c->opts.tlc_order && c->words == 1 &&
          L.bits - mb <= 31 && L.N >= 1 && L.N <= 8 && !c->opts.outdegree && L.nkv >= 1 && c->hm.n_init >= 1 &&
-         !c->opts.device_store_cap && !c->opts.fpset_spill && !(c->hm.user && jit_off());
+         !c->opts.device_store_cap && !c->opts.fpset_spill && !(c->hm.user && jit_off()) &&
+         c->hm.constraints.empty();
 }
 
 // the closed mode (tree.h): no Producer, a closed partition, components the
@@ -2640,7 +2697,7 @@ bool tree_closed_applicable(const tlcg_ctx* c) {
   return !L.producer && !(tv && std::atoi(tv) == 0) && c->closed && !c->opts.tlc_order && !c->opts.outdegree &&
          code_bits(L) <= 31 && L.N >= 1 && L.N <= 8 && (c->words == 1 || c->words == 2) &&
          c->hm.n_init >= 1 && c->hm.n_init < (1ull << 40) && !c->opts.device_store_cap && !c->opts.fpset_spill &&
-         !(c->hm.user && (jit_off() || L.msgs_mask_hi));
+         !(c->hm.user && (jit_off() || L.msgs_mask_hi)) && c->hm.constraints.empty();
 }
 
 // ---- the Producer tree's error, reported as TLC reports it ----
@@ -3172,7 +3229,7 @@ void ensure_user_check(tlcg_ctx* c) {
 // the least user-invariant event of the new level [g0, g0 + n) (NO_EVENT: none,
 // or no user invariants); ~0ull - 1 on a launch error
 u64 user_check_level(tlcg_ctx* c, u64 g0, u64 n, bool level0) {
-  if (!c->hm.user || !n) return NO_EVENT;
+  if (!c->hm.user || !c->hm.user->n_user || !n) return NO_EVENT;  // (a program of constraints alone: nothing here)
   unsigned long long h = NO_EVENT;
   if (hipMemcpyAsync(c->d_uev, &h, sizeof h, hipMemcpyHostToDevice, c->stream) != hipSuccess) return ~0ull - 1;
   const UserCheckArgs a = {dev_state(c, g0), dev_parent(c, g0), n, level0 ? 1 : 0, c->d_uev,
@@ -3199,6 +3256,130 @@ u64 user_check_level(tlcg_ctx* c, u64 g0, u64 n, bool level0) {
   return h;
 }
 
+bool ensure_constraint_scratch(tlcg_ctx* c, u64 n) {
+  if (!c->d_cev) {
+    if (!alloc_bytes(c, (void**)&c->d_cev, 8, "constraint event")) return false;
+    HIPCHK(hipEventCreate(&c->ce0));
+    HIPCHK(hipEventCreate(&c->ce1));
+  }
+  if (n <= c->con_cap) return true;
+  hipFree(c->d_ckeep); hipFree(c->d_ccnt); hipFree(c->d_ctmp); hipFree(c->d_cst); hipFree(c->d_cpar);
+  c->d_ckeep = nullptr;
+  c->d_ccnt = nullptr;
+  c->d_ctmp = nullptr;
+  c->d_cst = c->d_cpar = nullptr;
+  c->con_cap = 0;
+  const u64 cap = std::max<u64>(n + n / 4, 1u << 16), nb = (cap + BLOCK - 1) / BLOCK + 1;
+  if (nb > 0x7fffffffull) {
+    c->err = "a level too large for the constraint pass";
+    return false;
+  }
+  size_t tmp = 0;
+  HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, (const unsigned long long*)nullptr,
+                                          (unsigned long long*)nullptr, (int)nb, c->stream));
+  if (!alloc_bytes(c, (void**)&c->d_ckeep, cap, "constraint flags") ||
+      !alloc_bytes(c, (void**)&c->d_ccnt, 2 * nb * 8, "constraint block counts") ||
+      !alloc_bytes(c, &c->d_ctmp, std::max<size_t>(tmp, 8), "constraint scan scratch"))
+    return false;
+  if (!c->opts.tlc_order && (!alloc_bytes(c, (void**)&c->d_cst, cap * 8 * c->words, "constraint scratch") ||
+                             !alloc_bytes(c, (void**)&c->d_cpar, cap * 8, "constraint scratch")))
+    return false;
+  c->ctmp_bytes = std::max<size_t>(tmp, 8);
+  c->con_cap = cap;
+  return true;
+}
+
+// The constraint pass over the new level [g0, g0 + n) (cfg CONSTRAINT): the
+// states that satisfy every constraint stay, packed in their order, the others
+// leave the store (they stay in the FPSet until it is next rebuilt, which only
+// spares later levels their rediscovery).  Runs after the level's invariant
+// work -- invariants are checked on discarded states too -- and before the
+// level is committed.  Returns the kept count, ~0 on an error; *cev = the least
+// constraint-evaluation event of the level (NO_EVENT: none).
+u64 constraint_level(tlcg_ctx* c, u64 g0, u64 n, bool level0, u64* cev) {
+  *cev = NO_EVENT;
+  c->con_level_ms.push_back(0.f);
+  if (!n) return 0;
+  if (!ensure_constraint_scratch(c, n)) return ~0ull;
+  const u64 nb = (n + BLOCK - 1) / BLOCK;
+  unsigned long long* cnt = c->d_ccnt;
+  unsigned long long* off = c->d_ccnt + (c->con_cap + BLOCK - 1) / BLOCK + 1;
+  // (TLC order: the sort's scratch is free once k_tlc_finish has written the
+  // level back; level 0 is not sorted, so it may not exist yet)
+  if (c->opts.tlc_order && n > c->scratch_cap && !ensure_scratch(c, n)) return ~0ull;
+  u64* st2 = c->opts.tlc_order ? c->d_st2 : c->d_cst;
+  u64* par2 = c->opts.tlc_order ? c->d_dk2 : c->d_cpar;
+  if (c->opts.tlc_order && n > c->scratch_cap) {
+    c->err = "internal: TLC-order scratch smaller than the level";
+    return ~0ull;
+  }
+  unsigned long long h[2] = {NO_EVENT, 0};
+  HIPCHK_U(hipMemcpyAsync(c->d_cev, &h[0], 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK_U(hipMemsetAsync(cnt + nb, 0, 8, c->stream));  // (the scan's last entry: the total)
+  const ConstraintArgs a = {{dev_state(c, g0), dev_parent(c, g0), n, level0 ? 1 : 0, c->d_cev,
+                             (u64)c->opts.rank << 56, g0},
+                            c->d_ckeep, cnt};
+  ensure_user_check(c);  // (a hipRTC build on first use: host time, outside the timed window)
+  HIPCHK_U(hipEventRecord(c->ce0, c->stream));
+  if (c->ujit_state >= 1) {
+    if (!jit_launch_constraint_eval(c->ujit, a, c->stream)) {
+      c->err = "constraint kernel launch failed";
+      return ~0ull;
+    }
+  } else if (c->words == 1) {
+    k_constraint_eval<u64><<<(unsigned)nb, BLOCK, 0, c->stream>>>(c->hm.L, c->d_prog, a);
+  } else {
+    k_constraint_eval<u128><<<(unsigned)nb, BLOCK, 0, c->stream>>>(c->hm.L, c->d_prog, a);
+  }
+  HIPCHK_U(hipGetLastError());
+  size_t tmp = c->ctmp_bytes;
+  HIPCHK_U(hipcub::DeviceScan::ExclusiveSum(c->d_ctmp, tmp, (const unsigned long long*)cnt, off, (int)(nb + 1),
+                                            c->stream));
+  if (c->words == 1)
+    k_constraint_scatter<u64><<<(unsigned)nb, BLOCK, 0, c->stream>>>(dev_state(c, g0), dev_parent(c, g0), c->d_ckeep,
+                                                                     off, n, st2, par2);
+  else
+    k_constraint_scatter<u128><<<(unsigned)nb, BLOCK, 0, c->stream>>>((const u128*)dev_state(c, g0), dev_parent(c, g0),
+                                                                      c->d_ckeep, off, n, (u128*)st2, par2);
+  HIPCHK_U(hipGetLastError());
+  HIPCHK_U(hipEventRecord(c->ce1, c->stream));
+  HIPCHK_U(hipMemcpyAsync(&h[0], c->d_cev, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK_U(hipMemcpyAsync(&h[1], off + nb, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK_U(hipStreamSynchronize(c->stream));
+  const u64 kept = h[1];
+  if (kept > n) {
+    c->err = "internal: constraint pass count";
+    return ~0ull;
+  }
+  if (kept && kept < n) {
+    HIPCHK_U(hipMemcpyAsync(dev_state(c, g0), st2, kept * 8 * c->words, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK_U(hipMemcpyAsync(dev_parent(c, g0), par2, kept * 8, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK_U(hipStreamSynchronize(c->stream));
+  }
+  float ms = 0;
+  hipEventElapsedTime(&ms, c->ce0, c->ce1);
+  c->con_level_ms.back() = ms;
+  c->kernel_ms += ms;
+  c->con_discarded += n - kept;
+  c->con_in_fpset += n - kept;
+  *cev = h[0];
+  return kept;
+}
+
+// the level's event: the least of the invariant / deadlock / action events and
+// the constraint-evaluation event by discovery key; on the same state the
+// constraint's comes first (TLC evaluates the constraints before the
+// invariants).  Resolves it; a constraint error ends the run with
+// TLCG_CONSTRAINT_ERROR, its state found like a violating one.
+bool resolve_level_event(tlcg_ctx* c, u64 ev, u64 cev, int level) {
+  if (cev != NO_EVENT && (ev == NO_EVENT || (cev >> 6) <= (ev >> 6))) {
+    if (!resolve_event(c, cev, level)) return false;
+    c->status = TLCG_CONSTRAINT_ERROR;
+    return true;
+  }
+  return resolve_event(c, ev, level);
+}
+
 bool run_init(tlcg_ctx* c) {
   c->engine = TLCG_ENGINE_GLOBAL;
   const HostModel& hm = c->hm;
@@ -3220,7 +3401,10 @@ bool run_init(tlcg_ctx* c) {
   c->level_base.assign(1, 0);
   c->gen_at.clear();
   c->outdeg.assign(1, 0);
-  c->outdeg_valid = c->opts.outdegree && c->opts.tlc_order && c->opts.world == 1;
+  // (under a constraint a parent's discarded children are not in the level: no histogram)
+  c->outdeg_valid = c->opts.outdegree && c->opts.tlc_order && c->opts.world == 1 && hm.constraints.empty();
+  c->con_discarded = c->con_in_fpset = 0;
+  c->con_level_ms.clear();
   c->generated = 0;
   c->status = TLCG_RUNNING;
   c->ev_word = NO_EVENT;
@@ -3295,15 +3479,18 @@ bool run_init(tlcg_ctx* c) {
     }
     if (!rebuild_fpset(c, c->log2 + ((ovf & OVF_FPSET) ? 1 : 0), 0)) return false;
   }
-  const u64 n_new = world == 1 ? hm.n_init : c->h_ctr->n_new;
+  u64 n_new = world == 1 ? hm.n_init : c->h_ctr->n_new;
   c->generated = n_new;
+  const u64 uev = user_check_level(c, 0, n_new, true);
+  if (uev == ~0ull - 1) return false;
+  // every initial state is generated and checked; the ones in the model stay
+  u64 cev = NO_EVENT;
+  if (!hm.constraints.empty() && (n_new = constraint_level(c, 0, n_new, true, &cev)) == ~0ull) return false;
   // partitioned ranks keep every level (possibly empty) so that level d is
   // the same BFS level on every rank; termination is decided globally.
   if (n_new || world > 1) c->level_base.push_back(n_new);
-  const u64 uev = user_check_level(c, 0, n_new, true);
-  if (uev == ~0ull - 1) return false;
   const u64 ev = std::min<u64>(c->h_ctr->event, uev);
-  if (ev != NO_EVENT) return resolve_event(c, ev, 0);
+  if (ev != NO_EVENT || cev != NO_EVENT) return resolve_level_event(c, ev, cev, 0);
   if (!n_new && world == 1) c->status = TLCG_DONE;
   return true;
 }
@@ -3508,7 +3695,8 @@ bool step_level(tlcg_ctx* c) {
   const u64 worst = F * (u64)hm.max_new_per_state;
   const u64 est = next_level_estimate(c, F);
   if (!ensure_store(c, d + std::min(worst, std::max(est, (u64)1 << 20)))) return false;
-  if ((c->opts.log2_fpset_slots <= 0 || c->opts.fpset_spill) && !ensure_fpset(c, d + est)) return false;
+  if ((c->opts.log2_fpset_slots <= 0 || c->opts.fpset_spill) && !ensure_fpset(c, d + est + c->con_in_fpset))
+    return false;
   if (!ensure_scratch(c, std::min(worst, dev_room(c, d)))) return false;
   u64 room = store_room_hook(dev_room(c, d));
   for (;; room = dev_room(c, d)) {
@@ -3548,11 +3736,15 @@ bool step_level(tlcg_ctx* c) {
   c->gen_at.push_back(c->generated);
   c->generated += c->h_ctr->generated;
   if (c->outdeg_valid && !add_child_runs(c, d, n_new, F)) return false;
-  if (n_new) c->level_base.push_back(d + n_new);
   const u64 uev = user_check_level(c, d, n_new, false);
   if (uev == ~0ull - 1) return false;
+  // the level's invariant work is done (on the states about to be discarded
+  // too): the constraint pass decides which of them are stored and expanded
+  u64 cev = NO_EVENT;
+  if (!hm.constraints.empty() && (n_new = constraint_level(c, d, n_new, false, &cev)) == ~0ull) return false;
+  if (n_new) c->level_base.push_back(d + n_new);
   const u64 ev = std::min<u64>(c->h_ctr->event, uev);
-  if (ev != NO_EVENT) return resolve_event(c, ev, depth);
+  if (ev != NO_EVENT || cev != NO_EVENT) return resolve_level_event(c, ev, cev, depth);
   if (!n_new) c->status = TLCG_DONE;
   return true;
 }
@@ -3730,6 +3922,21 @@ int tlcg_create(const tlcg_model* m, const tlcg_opts* o, tlcg_ctx** out) {
     *out = c;
     return -2;
   }
+  if (!c->hm.constraints.empty()) {
+    // state constraints (cfg CONSTRAINT): the global engine on one rank, everything resident
+    const char* why = c->opts.world > 1 ? "a CONSTRAINT needs one rank (world == 1): the partitioned level does not filter"
+                      : c->opts.engine == TLCG_ENGINE_COMPONENT || c->opts.engine == TLCG_ENGINE_TREE
+                          ? "a CONSTRAINT changes the reachable set: the on-chip engines (component, component tree) "
+                            "do not take it; use the global engine (or auto)"
+                      : c->opts.spill ? "a CONSTRAINT is not combined with the host spill of the state store (spill)"
+                      : c->opts.fpset_spill ? "a CONSTRAINT is not combined with the host FPSet tier (fpset_spill)"
+                                            : nullptr;
+    if (why) {
+      c->err = why;
+      *out = c;
+      return -2;
+    }
+  }
   if (c->opts.engine == TLCG_ENGINE_TREE && !tree_applicable(c) && !tree_closed_applicable(c)) {
     c->err = "the component-tree engine needs a modelled Producer, one rank, <= 63-bit states, no TLC-order "
              "mode and no outdegree statistics";
@@ -3810,6 +4017,14 @@ void tlcg_destroy(tlcg_ctx* c) {
   hipFree(c->d_scratch);
   hipFree(c->d_prog);
   hipFree(c->d_uev);
+  hipFree(c->d_cev);
+  hipFree(c->d_ckeep);
+  hipFree(c->d_ccnt);
+  hipFree(c->d_ctmp);
+  hipFree(c->d_cst);
+  hipFree(c->d_cpar);
+  if (c->ce0) hipEventDestroy(c->ce0);
+  if (c->ce1) hipEventDestroy(c->ce1);
   tlcg_destroy(c->sub);
   c->sub = nullptr;
   jit_release(&c->jit);
@@ -4167,7 +4382,7 @@ int tlcg_trace_words(tlcg_ctx* c, uint64_t* states, int32_t* actions, int32_t ca
     }
     std::reverse(st.begin(), st.end());
     std::reverse(act.begin(), act.end());
-    if (c->status == TLCG_VIOLATION || c->status == TLCG_INVARIANT_ERROR) {
+    if (c->status == TLCG_VIOLATION || c->status == TLCG_INVARIANT_ERROR || c->status == TLCG_CONSTRAINT_ERROR) {
       st.push_back(c->ev_state);
       act.push_back(c->ev_action);
     }
@@ -4286,6 +4501,10 @@ int onchip_stop_stats(tlcg_ctx* c, uint64_t* generated, uint64_t* distinct, uint
 int tlcg_tlc_stop_stats(tlcg_ctx* c, uint64_t* generated, uint64_t* distinct, uint64_t* left_on_queue) {
   const DeviceGuard dg(c);
   if (!c) return -1;
+  if (!c->hm.constraints.empty()) {
+    c->err = "TLC stop statistics are not worked out for a model with a CONSTRAINT";
+    return -2;
+  }
   if (c->stop_cached && c->status >= TLCG_VIOLATION) {  // (worked out with the run: producer_error)
     *generated = c->stop_g;
     *distinct = c->stop_d;
@@ -4396,6 +4615,18 @@ int tlcg_tlc_stop_stats(tlcg_ctx* c, uint64_t* generated, uint64_t* distinct, ui
 
 // States generated per level (tlcgpu.h): out[0] = initial states, out[k] =
 // successors generated by expanding level k - 1.
+int tlcg_constraint_stats(tlcg_ctx* c, uint64_t* discarded, double* pass_ms, float* level_ms, int32_t cap,
+                          int32_t* n) {
+  if (!c) return -1;
+  if (discarded) *discarded = c->con_discarded;
+  double t = 0;
+  for (float x : c->con_level_ms) t += x;
+  if (pass_ms) *pass_ms = t;
+  for (size_t i = 0; level_ms && i < c->con_level_ms.size() && (int32_t)i < cap; ++i) level_ms[i] = c->con_level_ms[i];
+  if (n) *n = (int32_t)c->con_level_ms.size();
+  return 0;
+}
+
 int tlcg_level_generated(tlcg_ctx* c, uint64_t* out, int32_t cap, int32_t* n) {
   if (!c || !n) return -1;
   std::vector<u64> v;
@@ -4943,6 +5174,8 @@ int tlcg_recover(tlcg_ctx* c, const char* path, tlcg_stats* st) {
   c->level_base = lb;
   c->gen_at.clear();  // (not in the checkpoint: tlcg_tlc_stop_stats refuses after a recover)
   c->outdeg_valid = false;  // (nor the outdegree histogram of the levels before it)
+  c->con_discarded = 0;     // (the constraint pass's figures count from here on)
+  c->con_level_ms.clear();
   c->generated = h.generated;
   c->levels_redone = h.levels_redone;
   c->kernel_ms = h.kernel_ms;

@@ -731,11 +731,11 @@ class Compiler {
   }
 
   // compiles definition `name` as user invariant k
-  void compile(int k, const std::string& name) {
+  void compile(int k, const std::string& name, const std::string& kind = "invariant") {
     auto it = defs.find(name);
-    if (it == defs.end()) throw CompileError("invariant " + name + " is not defined");
-    if (!it->second.params.empty()) throw CompileError("invariant " + name + " takes arguments");
-    compile_def(k, it->second, "invariant " + name);
+    if (it == defs.end()) throw CompileError(kind + " " + name + " is not defined");
+    if (!it->second.params.empty()) throw CompileError(kind + " " + name + " takes arguments");
+    compile_def(k, it->second, kind + " " + name);
   }
   // compiles the body of d (a definition, or a part of one: a property's P or Q) as entry k
   void compile_def(int k, Def& d, const std::string& what, const std::string& at = std::string()) {
@@ -2211,6 +2211,7 @@ std::vector<Def> split_defs(const std::string& text) {
       cur = &out.back();
       continue;
     }
+    if (line.compare(0, 13, "@@CONSTRAINT ") == 0) continue;  // (user_constraint_names reads these)
     if (cur) cur->text += line + "\n";
   }
   return out;
@@ -2237,8 +2238,12 @@ bool prog_tables(const HostModel& hm, UserProg* P, std::string* err) {
 // named by m.invariants[q] - INV_USER) into P; false with a message naming
 // the invariant and the construct otherwise.
 bool compile_user_invariants(const tlcg_model& m, const HostModel& hm, const std::vector<std::string>& names,
-                             UserProg* P, std::string* err) {
+                             UserProg* P, std::string* err, const std::vector<std::string>& constraints) {
   if (!prog_tables(hm, P, err)) return false;
+  if (names.size() > (size_t)TLCG_MAX_INV || constraints.size() > (size_t)TLCG_MAX_INV) {
+    *err = "more than " + std::to_string(TLCG_MAX_INV) + " user invariants or constraints";
+    return false;
+  }
   Compiler c(hm, P);
   for (Def& d : split_defs(m.user_defs ? m.user_defs : "")) c.defs[d.name] = d;
   P->n_user = (int32_t)names.size();
@@ -2247,6 +2252,16 @@ bool compile_user_invariants(const tlcg_model& m, const HostModel& hm, const std
       c.compile((int)k, names[k]);
     } catch (const CompileError& e) {
       *err = "invariant " + names[k] + " cannot be checked: " + e.what();
+      return false;
+    }
+  }
+  // the constraints: the same subset, further entries after the invariants
+  P->n_con = (int32_t)constraints.size();
+  for (size_t k = 0; k < constraints.size(); ++k) {
+    try {
+      c.compile((int)(names.size() + k), constraints[k], "constraint");
+    } catch (const CompileError& e) {
+      *err = "constraint " + constraints[k] + " cannot be checked: " + e.what();
       return false;
     }
   }
@@ -2804,7 +2819,8 @@ std::string user_device_source(const UserProg& P, const Layout& L) {
   o << "namespace tlcg {\n";
   const int n = P.n_ins;
   std::vector<bool> target((size_t)n + 1, false);
-  for (int k = 0; k < P.n_user; ++k) target[(size_t)P.entry[k]] = true;
+  const int n_entry = P.n_user + P.n_con;  // (the constraints' functions follow the invariants')
+  for (int k = 0; k < n_entry; ++k) target[(size_t)P.entry[k]] = true;
   for (int i = 0; i < n; ++i) {
     const UInsn& in = P.ins[i];
     if (in.op == U_JMP || in.op == U_JZ || in.op == U_JNZ) target[(size_t)in.imm] = true;
@@ -2814,7 +2830,7 @@ std::string user_device_source(const UserProg& P, const Layout& L) {
     maxreg = std::max({maxreg, (int)P.ins[i].a + 1, (int)P.ins[i].b + 1, (int)P.ins[i].c + 1});
   maxreg = std::max(maxreg, 1);
   auto R = [](int r) { return "r" + std::to_string(r); };
-  for (int k = 0; k < P.n_user; ++k) {
+  for (int k = 0; k < n_entry; ++k) {
     o << "template <class V>\nTLCG_HD int tlcg_user_inv_" << k << "(const V& v) {\n";
     o << "  long long ";
     for (int r = 0; r < maxreg; ++r) o << R(r) << " = 0" << (r + 1 < maxreg ? ", " : ";\n");
@@ -2909,8 +2925,14 @@ std::string user_device_source(const UserProg& P, const Layout& L) {
     o << "  return EV_ERROR;\n}\n";
   }
   o << "template <class V>\nTLCG_HD int tlcg_user_eval(int k, const V& v) {\n  switch (k) {\n";
-  for (int k = 0; k < P.n_user; ++k) o << "    case " << k << ": return tlcg_user_inv_" << k << "(v);\n";
+  for (int k = 0; k < n_entry; ++k) o << "    case " << k << ": return tlcg_user_inv_" << k << "(v);\n";
   o << "  }\n  return EV_ERROR;\n}\n";
+  // the conjunction of the constraints, left to right (kernels.h
+  // constraint_eval_body; user_inv.h eval_constraints_v is the interpreter's)
+  o << "template <class V>\nTLCG_HD int tlcg_constraints_eval(const V& v, int* which) {\n  int r = EV_TRUE;\n  (void)r;\n";
+  for (int k = 0; k < P.n_con; ++k)
+    o << "  r = tlcg_user_inv_" << P.n_user + k << "(v);\n  if (r != EV_TRUE) { *which = " << k << "; return r; }\n";
+  o << "  return EV_TRUE;\n}\n";
   // the outcome tables (component_code.h code_consts_user): an invariant whose
   // program reads at most UTAB_BITS code bits gets 2 bits per pattern of them
   // in CodeConsts::utab, while its 64 bits last; worked out here for every
@@ -2986,6 +3008,19 @@ std::string user_device_source(const UserProg& P, const Layout& L) {
 std::vector<std::string> user_def_names(const char* text) {
   std::vector<std::string> out;
   for (const Def& d : split_defs(text ? text : "")) out.push_back(d.name);
+  return out;
+}
+
+// the names its "@@CONSTRAINT <name>" lines give, in order
+std::vector<std::string> user_constraint_names(const char* text) {
+  std::vector<std::string> out;
+  std::istringstream in(text ? text : "");
+  for (std::string line; std::getline(in, line);) {
+    if (line.compare(0, 13, "@@CONSTRAINT ") != 0) continue;
+    std::istringstream h(line.substr(13));
+    std::string nm;
+    if (h >> nm) out.push_back(nm);
+  }
   return out;
 }
 

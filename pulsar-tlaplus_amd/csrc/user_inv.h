@@ -84,7 +84,8 @@ struct UInsn {
 struct UserProg {
   int32_t n_user;                 // user invariants
   int32_t n_ins;
-  int32_t entry[8];               // first instruction of user invariant k
+  int32_t n_con;                  // state constraints (cfg CONSTRAINT): entries n_user .. n_user + n_con - 1
+  int32_t entry[16];              // first instruction of user invariant k, then of each constraint
   int32_t nk, nv;                 // |KeySet|, |ValueSet|
   int32_t keyval[UI_MAXSET];      // key index -> value (model.h: index 0 = NullKey = 0)
   int32_t valval[UI_MAXSET];      // value index -> value
@@ -297,6 +298,21 @@ TLCG_HD int check_invariants_all(const Layout& L, const UserProg& P, W s) {
     if (r != EV_TRUE) return (q << 1) | (r == EV_ERROR ? 1 : 0);
   }
   return -1;
+}
+
+// The conjunction of the model's state constraints on the state behind view
+// v, left to right (TLC's isInModel): EV_TRUE in the model, EV_FALSE discarded,
+// EV_ERROR with *which = the failing constraint.
+template <class V>
+TLCG_HD int eval_constraints_v(const UserProg& P, const V& v, int* which) {
+  for (int k = 0; k < P.n_con; ++k) {
+    const int r = eval_user_v(P, P.n_user + k, v);
+    if (r != EV_TRUE) {
+      *which = k;
+      return r;
+    }
+  }
+  return EV_TRUE;
 }
 
 }  // namespace tlcg

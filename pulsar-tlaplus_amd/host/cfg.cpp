@@ -163,6 +163,8 @@ struct CfgParser {
         names(&c->invariants);
       } else if (kw == "PROPERTY" || kw == "PROPERTIES") {
         names(&c->properties);
+      } else if (kw == "CONSTRAINT" || kw == "CONSTRAINTS") {
+        names(&c->constraints);
       } else if (kw == "SPECIFICATION" || kw == "INIT" || kw == "NEXT") {
         if (cur().k != Tok::ID || is_kw()) return fail(kw + " needs a name");
         (kw == "SPECIFICATION" ? c->specification : kw == "INIT" ? c->init : c->next) = cur().t;
@@ -631,6 +633,35 @@ bool bind_model(const Config& cfg, const Module& mod, bool deadlock_flag, tlcg_m
       continue;
     }
     m->invariants[m->n_invariants++] = id;
+  }
+  // CONSTRAINT(S): state predicates of the module, resolved like the user
+  // invariants and compiled by the same front end (a conjunction; only states
+  // that satisfy it are stored and expanded); they travel as "@@CONSTRAINT
+  // name" lines after the definitions
+  if (cfg.constraints.size() > TLCG_MAX_INV) {
+    *err = "Error: too many constraints";
+    return false;
+  }
+  for (auto& name : cfg.constraints) {
+    if (!mod.find(name)) {
+      *err = "Error: The constraint " + name + " specified in the configuration file is not defined in the specification.";
+      return false;
+    }
+    ensure_defs();
+    if (index.find(name) == index.end()) {
+      *err = "Error: constraint " + name + " cannot be checked: its definition text is not available.";
+      return false;
+    }
+  }
+  if (!cfg.constraints.empty()) {
+    if (!cfg.properties.empty()) {
+      *err = "Error: this checker does not check a PROPERTY under a CONSTRAINT (" + cfg.properties[0] + ", " +
+             cfg.constraints[0] + "): the temporal and action property passes walk the unconstrained graph.";
+      return false;
+    }
+    if (!defs.empty() && defs.back() != '\n') defs += "\n";
+    for (auto& name : cfg.constraints) defs += "@@CONSTRAINT " + name + "\n";
+    m->user_defs = defs.c_str();
   }
   // a PROPERTY other than Termination as published: a definition the temporal
   // front end of libtlcgpu (user_inv.cpp) takes -- <>Q, []<>Q, P ~> Q over

@@ -24,12 +24,13 @@ struct Config {
   std::vector<std::string> order;          // constants in file order
   std::vector<std::string> invariants;     // INVARIANT(S), file order
   std::vector<std::string> properties;     // PROPERTY/PROPERTIES
+  std::vector<std::string> constraints;    // CONSTRAINT(S), file order
   std::string specification, init, next;
   int check_deadlock = -1;                 // CHECK_DEADLOCK TRUE/FALSE, -1 unset
 };
 
 // Parses the TLC cfg grammar subset: CONSTANT(S), SPECIFICATION, INIT, NEXT,
-// INVARIANT(S), PROPERTY/PROPERTIES, CHECK_DEADLOCK; `\*` and nested `(* *)`
+// INVARIANT(S), PROPERTY/PROPERTIES, CONSTRAINT(S), CHECK_DEADLOCK; `\*` and nested `(* *)`
 // comments; values are integers, strings, TRUE/FALSE, {sets}, model values.
 bool parse_cfg(const std::string& text, Config* out, std::string* err);
 

@@ -242,6 +242,16 @@ int main(int argc, char** argv) {
   opts.spill = 1;
   opts.fpset_spill = tlcg_state_words(&model) == 1;  // and TLC's DiskFPSet: the host tier (narrow states)
   opts.outdegree = 1;  // TLC's outdegree line
+  if (!cfg.constraints.empty()) {
+    // a CONSTRAINT: the global engine on one GPU with everything resident
+    // (the outdegree line is left out: discarded successors are not in the levels)
+    if (o.gpus > 1) {
+      std::printf("Error: a cfg with a CONSTRAINT is checked on one GPU (-gpus 1).\n");
+      return 255;
+    }
+    opts.spill = opts.fpset_spill = 0;
+    opts.outdegree = 0;
+  }
   if (!recover_file.empty()) opts.engine = TLCG_ENGINE_GLOBAL;  // checkpoints are global-engine level states
   else std::printf("Computing initial states...\n");
   tlcg_ctx* ctx = nullptr;
@@ -511,6 +521,11 @@ int main(int argc, char** argv) {
         std::printf("Error: Evaluating invariant %s failed.\n", cfg.invariants[(size_t)tst.invariant].c_str());
         rc = 75;
         break;
+      case TLCG_CONSTRAINT_ERROR:
+        // (tst.invariant: the index of the constraint in the cfg's order)
+        std::printf("Error: Evaluating constraint %s failed.\n", cfg.constraints[(size_t)tst.invariant].c_str());
+        rc = 75;
+        break;
       case TLCG_DEADLOCK:
         std::printf("Error: Deadlock reached.\n");
         rc = 11;
@@ -547,7 +562,9 @@ int main(int argc, char** argv) {
     }
     // TLC stops mid-level: its counts at that moment (else the end of the level)
     uint64_t sg = 0, sd = 0, sq = 0;
-    if (tctx && tlcg_tlc_stop_stats(tctx, &sg, &sd, &sq) == 0) {
+    if (!cfg.constraints.empty()) {
+      // (under a CONSTRAINT the counts are at the end of the level, in-model states: [TLC-ext])
+    } else if (tctx && tlcg_tlc_stop_stats(tctx, &sg, &sd, &sq) == 0) {
       st.generated = sg;
       st.distinct = sd;
       stop_left = sq;

@@ -26,7 +26,8 @@ INV_USER = 16  # TLCG_INV_USER: invariants[q] = INV_USER + j names the j-th user
 ACTIONS = ("Producer", "CompactorPhaseOne", "CompactorPhaseTwoWrite", "CompactorPhaseTwoUpdateContext",
            "CompactorPhaseTwoUpdateHorizon", "CompactorPhaseTwoPersistCusror", "CompactorPhaseTwoDeleteLedger",
            "BrokerCrash", "Consumer", "Terminating")
-STATUS = {0: "running", 1: "ok", 2: "invariant", 3: "deadlock", 4: "action_error", 5: "invariant_error"}
+STATUS = {0: "running", 1: "ok", 2: "invariant", 3: "deadlock", 4: "action_error", 5: "invariant_error",
+          6: "constraint_error"}
 ENGINES = {"auto": 0, "global": 1, "component": 2, "tree": 3}
 ENGINE_NAMES = {1: "global", 2: "component", 3: "tree"}
 
@@ -196,6 +197,9 @@ def load_library(path: str = LIB_PATH):
         "tlcg_action_eval_selftest": (C.c_int, [M, O, C.c_char_p, C.POINTER(U64), U64, C.POINTER(C.c_uint8),
                                                 C.c_char_p, I32]),
         "tlcg_jit_selftest": (C.c_int, [M, C.c_char_p, I32, C.c_char_p, I32][:1] + [C.c_char_p, C.c_char_p, I32]),
+        "tlcg_host_constraint_eval": (C.c_int, [M, C.POINTER(U64), U64, C.POINTER(C.c_uint8), C.c_char_p, I32]),
+        "tlcg_constraint_stats": (C.c_int, [P, C.POINTER(U64), C.POINTER(C.c_double), C.POINTER(C.c_float), I32,
+                                            C.POINTER(I32)]),
         "tlcg_user_eval_selftest": (C.c_int, [M, O, C.POINTER(U64), U64, I32, C.POINTER(C.c_uint8), C.c_char_p, I32]),
     }
     for name, (res, args) in sig.items():
@@ -225,17 +229,24 @@ class Model:
     # ones (include/tlcgpu.h tlcg_model.user_defs).  A name here shadows the
     # spec's invariant of that name.
     user_defs: Optional[dict] = None
+    # a cfg's CONSTRAINT section: names of user_defs (state predicates without
+    # parameters), a conjunction; only states satisfying it are stored and
+    # expanded (include/tlcgpu.h tlcg_model.user_defs, "@@CONSTRAINT")
+    constraints: Optional[List[str]] = None
 
     def user_defs_text(self) -> Optional[str]:
-        """tlcg_model.user_defs: a "@@DEF name params" header line per definition, then its body"""
-        if not self.user_defs:
+        """tlcg_model.user_defs: a "@@DEF name params" header line per definition, then its body;
+        after the definitions a "@@CONSTRAINT name" line per constraint"""
+        if not self.user_defs and not self.constraints:
             return None
         out = []
-        for head, body in self.user_defs.items():
+        for head, body in (self.user_defs or {}).items():
             name, _, rest = head.partition("(")
             params = [p.strip() for p in rest.rstrip(")").split(",") if p.strip()]
             out.append("@@DEF " + " ".join([name.strip()] + params))
             out.append(body)
+        for name in self.constraints or ():
+            out.append("@@CONSTRAINT " + name)
         return "\n".join(out) + "\n"
 
     def user_names(self) -> List[str]:
@@ -445,6 +456,25 @@ def user_eval_states(model: Model, states: Sequence[int], path: str, device: int
         raise RuntimeError(f"tlcg_user_eval_selftest: {rc}: {err.value.decode()}")
     raw = bytes(out)[:n * nu]
     return [raw[k::nu] for k in range(nu)]
+
+
+def host_constraint_eval(model: Model, states: Sequence[int]) -> List[int]:
+    """The conjunction of model.constraints on each state, by the host interpreter
+    (tlcg_host_constraint_eval): 0 TRUE (in the model), 1 FALSE, 2 evaluation error."""
+    lib = load_library()
+    m = model.to_c()
+    w = state_words(model)
+    n = len(states)
+    buf = (C.c_uint64 * (max(n, 1) * w))()
+    for i, s in enumerate(states):
+        for j, x in enumerate(_to_words(s, w)):
+            buf[i * w + j] = x
+    out = (C.c_uint8 * max(n, 1))()
+    err = C.create_string_buffer(1024)
+    rc = lib.tlcg_host_constraint_eval(C.byref(m), buf, n, out, err, 1024)
+    if rc != 0:
+        raise RuntimeError(f"tlcg_host_constraint_eval: {err.value.decode()} ({rc})")
+    return [out[i] for i in range(n)]
 
 
 def host_check_invariants(model: Model, state: int) -> int:
@@ -796,6 +826,7 @@ class Result:
     transport: str = ""  # multi-rank runs: "local" (threads, device copies) or "rccl"
     tlc_exact: bool = False  # an error whose trace and tlc_stop_stats() are TLC -workers 1's (tlcg_stats.tlc_exact)
     jit_used: int = 0  # tlcg_stats.jit_used: which specialized kernels ran (include/tlcgpu.h)
+    constraint: Optional[str] = None  # status "constraint_error": the constraint that failed to evaluate
 
 
 class Checker:
@@ -913,6 +944,15 @@ class Checker:
         self._chk(self.lib.tlcg_outdegree(self.ctx, buf, 4100, C.byref(n)), "tlcg_outdegree")
         return [buf[i] for i in range(n.value)]
 
+    def constraint_stats(self) -> Tuple[int, float, List[float]]:
+        """(states the constraint pass discarded, its device time in ms, that time per level)
+        (tlcg_constraint_stats)"""
+        d, ms, n = C.c_uint64(), C.c_double(), C.c_int32()
+        lv = (C.c_float * 65536)()
+        self._chk(self.lib.tlcg_constraint_stats(self.ctx, C.byref(d), C.byref(ms), lv, 65536, C.byref(n)),
+                  "tlcg_constraint_stats")
+        return d.value, ms.value, [lv[i] for i in range(min(n.value, 65536))]
+
     def state_at(self, gidx: int) -> Tuple[int, int]:
         s, p = (C.c_uint64 * 2)(), C.c_uint64()
         self._chk(self.lib.tlcg_state_at_words(self.ctx, gidx, s, C.byref(p)), "tlcg_state_at_words")
@@ -927,7 +967,9 @@ class Checker:
                    expand_ms=s.expand_ms, levels_redone=s.levels_redone,
                    engine={v: k for k, v in ENGINES.items()}.get(s.engine, "?"), host_states=s.host_states,
                    fpset_host_states=s.fpset_host_states, tlc_exact=bool(s.tlc_exact), jit_used=s.jit_used)
-        if s.invariant >= 0:
+        if status == "constraint_error":  # (the index names the constraint)
+            r.constraint = (self.model.constraints or [None])[max(s.invariant, 0)]
+        elif s.invariant >= 0:
             r.invariant = self.model.invariants[s.invariant]
         if s.action >= 0:
             r.action = ACTIONS[s.action]
